@@ -12,17 +12,23 @@ train_an_epoch.  Everything an epoch does on top of the resident triples is INSI
 per-epoch device shuffle, the staging of the epoch (per-batch sort by item + layout; it runs on a side
 stream while the previous epoch trains), the 245 fused steps and the flush launch that applies the last update.
 
-Timing (>= 200 timed steps, median of >= 5 repeats): after W warm-up steps the next K steps
-are timed, R = max(5, ceil(200 / K)) times in a row (each repeat continues where the last one stopped, across
-epoch boundaries); `ms_per_step` is the MEDIAN over the repeats of (time of the K steps / K), `value` follows
-from it, `steps` stays K and `repeats` says R; `wall_ms_per_step` is the plain wall clock of the whole R x K
-region (launch latency of the first step included) for cross-checking.  N = 1: the repeats are enqueued back
-to back and delimited by HIP events on the stream they run on (a host synchronize per 0.2 ms window would
-measure the synchronize).  N > 1: the same events per rank, the whole R x K region bracketed by barrier +
-torch.cuda.synchronize() on both sides, and the MAX over ranks taken per repeat afterwards.
+Timing: after W warm-up steps exactly K steps are timed (`--steps K`; SURVEY.md §8d asks for >= 200 timed
+steps, which the default K = 2000 gives).  They run as R = min(5, K // 20) consecutive windows (at least one) of
+nearly equal length, continuing across epoch boundaries; `ms_per_step` is the MEDIAN over the windows of (time of
+the window / its steps), `value` follows from it, `steps` and `timed_steps_total` are K and `repeats` says R;
+`wall_ms_per_step` is the plain wall clock of the whole K-step region for cross-checking (at N = 1 it starts when
+the warm-up is enqueued, so it includes what of the warm-up was still running).  A window is no shorter than 20
+steps so that the host keeps enqueueing ahead of the GPU.  N = 1: the windows are enqueued right behind the
+warm-up steps, back to back, and delimited by HIP events on the stream they run on (a host synchronize per 0.2 ms
+window would measure the synchronize).  N > 1: the same events per rank, the whole K-step
+region bracketed by barrier + torch.cuda.synchronize() on both sides, and the MAX over ranks taken per window
+afterwards.
 
-`python bench.py --gpus N` without a torch.distributed environment starts its own N ranks (re-exec
-through torch.distributed.run on 127.0.0.1); under torchrun it uses RANK / LOCAL_RANK / WORLD_SIZE as
+`--dump-outputs DIR` writes, after the timed steps, what the timed path hands its caller: the model's parameters
+(and the step statistics) once the epoch in flight is finished, as DIR/<name>.npy (see dump_outputs).
+
+`python bench.py --gpus N` without a torch.distributed environment starts its own N ranks (a child
+torch.distributed.run on 127.0.0.1); under torchrun it uses RANK / LOCAL_RANK / WORLD_SIZE as
 given.  Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -32,6 +38,7 @@ import json
 import os
 import socket
 import statistics
+import subprocess
 import sys
 import time
 
@@ -46,7 +53,7 @@ if ROOT not in sys.path:
 U, I, D, B = 6040, 3706, 64, 4096
 LR = 0.05
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec peak)
-MIN_TIMED_STEPS, MIN_REPEATS = 200, 5
+MIN_TIMED_STEPS, MIN_REPEATS, MIN_WINDOW_STEPS = 200, 5, 20
 EPOCH_STEPS = 245  # N = 1 000 000 triples per epoch -> 245 batches of 4096 (1 003 520 triples)
 ROUND = "r06"
 
@@ -64,7 +71,14 @@ def optimizer_sweep_bytes(optimizer, n_params):
 
 
 def n_repeats(steps):
-    return max(MIN_REPEATS, -(-MIN_TIMED_STEPS // max(steps, 1)))
+    """Number of timing windows the K timed steps are split into."""
+    return max(1, min(MIN_REPEATS, steps // MIN_WINDOW_STEPS))
+
+
+def window_sizes(steps):
+    """The K timed steps as n_repeats(K) consecutive windows of nearly equal length (they sum to K)."""
+    R = n_repeats(steps)
+    return [steps // R + (r < steps % R) for r in range(R)]
 
 
 def _barrier(group, device):
@@ -77,26 +91,30 @@ def _barrier(group, device):
     torch.cuda.synchronize()
 
 
-def timed_repeats(run_epoch, steps, device, dist_on=False, group=None):
-    """Run `run_epoch(r)` (which enqueues exactly `steps` steps incl. their per-epoch staging) R times.
-    Returns (per-repeat seconds, wall seconds of the whole region).  See the module docstring."""
-    R = n_repeats(steps)
+def timed_repeats(run_window, steps, device, dist_on=False, group=None):
+    """Time exactly `steps` steps as the windows of window_sizes(steps): `run_window(done, n)` enqueues the n steps
+    that follow the `done` timed steps before them (incl. their per-epoch staging).  Returns (per-window seconds per
+    step, wall seconds of the whole region).  See the module docstring."""
+    sizes = window_sizes(steps)
+    R = len(sizes)
+    starts = [sum(sizes[:r]) for r in range(R)]
     if not dist_on:
+        # no host synchronize between the warm-up and the first window: the timed steps queue up behind the warm-up
+        # ones instead of starting on an idle GPU (whose restart a short K would otherwise time as a step)
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(R + 1)]
-        torch.cuda.synchronize()
         t0 = time.perf_counter()
         evs[0].record()
         for r in range(R):
-            run_epoch(r)
+            run_window(starts[r], sizes[r])
             evs[r + 1].record()
         torch.cuda.synchronize()
         wall = time.perf_counter() - t0
-        return [evs[r].elapsed_time(evs[r + 1]) * 1e-3 for r in range(R)], wall
+        return [evs[r].elapsed_time(evs[r + 1]) * 1e-3 / sizes[r] for r in range(R)], wall
     from beta_recsys_amd import _dist
 
-    # N > 1: the WHOLE region (R x K steps) is bracketed by barrier + synchronize on both sides; inside it every
-    # rank delimits its K-step windows with HIP events on the stream the steps run on -- exactly like N = 1 -- and
-    # the per-window times are MAX-reduced over the ranks afterwards.  (Bracketing every 20-step window with
+    # N > 1: the WHOLE region (K steps) is bracketed by barrier + synchronize on both sides; inside it every rank
+    # delimits its windows with HIP events on the stream the steps run on -- exactly like N = 1 -- and the
+    # per-window times are MAX-reduced over the ranks afterwards.  (Bracketing every 20-step window with
     # synchronize + barrier + synchronize measured the brackets: 14.9 us/step at --steps 20 against 12.5 at 2000 for
     # the same world-1 replicated step, VERDICT r2.)  The steps' own collectives keep the ranks in lock step.
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(R + 1)]
@@ -104,30 +122,31 @@ def timed_repeats(run_epoch, steps, device, dist_on=False, group=None):
     t0 = time.perf_counter()
     evs[0].record()
     for r in range(R):
-        run_epoch(r)
+        run_window(starts[r], sizes[r])
         evs[r + 1].record()
     _barrier(group, device)
     wall = time.perf_counter() - t0
-    per = [evs[r].elapsed_time(evs[r + 1]) * 1e-3 for r in range(R)]
+    per = [evs[r].elapsed_time(evs[r + 1]) * 1e-3 / sizes[r] for r in range(R)]
     t = torch.tensor(per + [wall], dtype=torch.float64, device=device)
-    _dist.all_reduce(t, op=_dist.ReduceOp.MAX, group=group)  # the slowest rank defines every repeat
+    _dist.all_reduce(t, op=_dist.ReduceOp.MAX, group=group)  # the slowest rank defines every window
     t = t.cpu().tolist()
     return t[:-1], t[-1]
 
 
 def timing_fields(per, wall, steps, units_per_step, world=1):
-    """The contract's fields from the per-repeat times: median epoch time / K."""
+    """The contract's fields from the per-window seconds per step: their median is the step time."""
     med = statistics.median(per)
-    return {"value": world * units_per_step * steps / med, "ms_per_step": med / steps * 1e3,
-            "repeats": len(per), "timed_steps_total": len(per) * steps,
-            "ms_per_step_by_repeat": [round(t / steps * 1e3, 5) for t in per],
-            "ms_per_step_min": min(per) / steps * 1e3, "ms_per_step_max": max(per) / steps * 1e3,
-            "wall_ms_per_step": wall / (len(per) * steps) * 1e3}
+    return {"value": world * units_per_step / med, "ms_per_step": med * 1e3,
+            "repeats": len(per), "timed_steps_total": steps,
+            "ms_per_step_by_repeat": [round(t * 1e3, 5) for t in per],
+            "ms_per_step_min": min(per) * 1e3, "ms_per_step_max": max(per) * 1e3,
+            "wall_ms_per_step": wall / steps * 1e3}
 
 
 def self_launch(n):
-    """`python bench.py --gpus N` without RANK / WORLD_SIZE: become `torch.distributed.run` with N ranks on
-    this node (one process per GPU over RCCL), same arguments."""
+    """`python bench.py --gpus N` without RANK / WORLD_SIZE: run `torch.distributed.run` with N ranks on this node
+    (one process per GPU over RCCL), same arguments, as a child process, and exit with its status.  (This process
+    has initialised the HIP runtime to count the GPUs, so it starts a fresh one rather than replacing itself.)"""
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if have < n:
         raise SystemExit(f"bench.py --gpus {n}: needs {n} visible MI355X GPUs, this node shows {have} "
@@ -140,7 +159,7 @@ def self_launch(n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    raise SystemExit(subprocess.run(cmd).returncode)
 
 
 def synth_triples(n, seed):
@@ -317,7 +336,7 @@ def bench_ncf(args, device, world=1, rank=0, dist_on=False):
             eng._enqueue_step(users[sl], items[sl], ratings[sl])
 
     run(0, W)
-    per, wall = timed_repeats(lambda r: run(W * B, K), K, device, dist_on)
+    per, wall = timed_repeats(lambda done, n: run((W + done) * B, n), K, device, dist_on)
     st = eng._sync_stats()
     if rank != 0:
         return None
@@ -380,7 +399,7 @@ def bench_mf_c4shard(args, device, full=False):
     torch.manual_seed(2020)
     with contextlib.redirect_stdout(io.StringIO()):
         eng = hp.MFEngine(cfg)
-    steps, warm = min(args.steps, 100), min(args.warmup, 10)
+    steps, warm = min(args.steps, 5 * 100), min(args.warmup, 10)   # windows of up to 100 steps
     full_cov = args.epoch_coverage == "full"
     # "sample": 50 steps = 3.3 M triples per epoch, users drawn uniformly -- at the whole-table size an epoch meets
     # 28 % of the users.  "full": EVERY user and item row occurs in every epoch (a data set in which every user has
@@ -423,7 +442,7 @@ def bench_mf_c4shard(args, device, full=False):
             n -= take
 
     advance(warm)
-    per, wall = timed_repeats(lambda r: advance(steps), steps, device)
+    per, wall = timed_repeats(lambda done, n: advance(n), steps, device)
     advance((epoch_steps - state["pos"]) % epoch_steps)
     # two WHOLE epochs of continuous training between one event pair (staging on the side stream, every step, the
     # epoch's flush): what a K-step window's median hides when K is shorter than an epoch
@@ -573,7 +592,7 @@ def bench_mf_c4_sharded(args, device, world, rank, group=None):
         eng.prefetch_setup()   # likewise the side stream / process group of the prefetched plans
     import beta_recsys_amd as hp
 
-    steps, warm = min(args.steps, 100), min(args.warmup, 10)
+    steps, warm = min(args.steps, 5 * 100), min(args.warmup, 10)   # windows of up to 100 steps
     epoch_steps = 50
     n_total = epoch_steps * Bc
     g = torch.Generator().manual_seed(5 + rank)
@@ -598,7 +617,7 @@ def bench_mf_c4_sharded(args, device, world, rank, group=None):
             n -= take
 
     advance(warm)
-    per, wall = timed_repeats(lambda r: advance(steps), steps, device, dist_on=True, group=group)
+    per, wall = timed_repeats(lambda done, n: advance(n), steps, device, dist_on=True, group=group)
     eng.k.check_status()
     exchange = plan_exchange_bytes(state["plan"], Dc)
     if rank != 0:
@@ -712,7 +731,7 @@ def bench_lightgcn(args, device, world=1, rank=0, dist_on=False):
             eng._enqueue_step((users[sl], pos[sl], neg[sl]))
 
     run(0, W)
-    per, wall = timed_repeats(lambda r: run(W * Bl, K), K, device, dist_on)
+    per, wall = timed_repeats(lambda done, n: run((W + done) * Bl, n), K, device, dist_on)
     st = eng._sync_stats()
     if rank != 0:
         return None
@@ -828,8 +847,8 @@ def bench_siblings(args, device):
         eng.enqueue_epoch(*batch_of(slice(lo, lo + n * Bs)))
 
     run(0, args.warmup)
-    per, wall = timed_repeats(lambda r: run(args.warmup * Bs, args.steps), args.steps, device)
-    dt = statistics.median(per)   # median over the repeats of one {args.steps}-step pass
+    per, wall = timed_repeats(lambda done, n: run((args.warmup + done) * Bs, n), args.steps, device)
+    dt = statistics.median(per) * args.steps   # the median window's step time, for the whole {args.steps} steps
     st = eng._sync_stats()
     out = {"metric": f"training interactions/sec ({args.workload} triples)", "value": args.steps * Bs / dt,
            "unit": unit, "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -850,8 +869,7 @@ def bench_siblings(args, device):
         else:
             make = lambda: torch_port.TorchT2VPort(w0, Bs, "adam", 5e-4)  # noqa: E731
         out["cpu_baseline"] = port_baseline(make, host, Bs, f"batch {Bs} (same workload)")
-    out.update(repeats=len(per), timed_steps_total=len(per) * args.steps,
-               wall_ms_per_step=wall / (len(per) * args.steps) * 1e3)
+    out.update(repeats=len(per), timed_steps_total=args.steps, wall_ms_per_step=wall / args.steps * 1e3)
     return out
 
 
@@ -881,8 +899,8 @@ def bench_ngcf(args, device):
             eng._enqueue_step((users[sl], pos[sl], neg[sl]))
 
     run(0, args.warmup)
-    per, wall = timed_repeats(lambda r: run(args.warmup * Bn, args.steps), args.steps, device)
-    dt = statistics.median(per)   # median over the repeats of one {args.steps}-step pass
+    per, wall = timed_repeats(lambda done, n: run((args.warmup + done) * Bn, n), args.steps, device)
+    dt = statistics.median(per) * args.steps   # the median window's step time, for the whole {args.steps} steps
     st = eng._sync_stats()
     nnz, N = adj.nnz, U + I
     act = N * D * 4                      # one [N, D] fp32 activation
@@ -918,8 +936,7 @@ def bench_ngcf(args, device):
                 for k in range(8)]
         make = lambda: torch_port.TorchNGCFPort(w0, norm.coalesce(), [0.1] * L, 1e-5, Bn, "adam", 0.05)  # noqa: E731
         out["cpu_baseline"] = port_baseline(make, host, Bn, f"batch {Bn} on the same graph")
-    out.update(repeats=len(per), timed_steps_total=len(per) * args.steps,
-               wall_ms_per_step=wall / (len(per) * args.steps) * 1e3)
+    out.update(repeats=len(per), timed_steps_total=args.steps, wall_ms_per_step=wall / args.steps * 1e3)
     return out
 
 
@@ -1133,17 +1150,19 @@ def bench_mf(args, device, world, rank, dist_on, force_mode=None, force_scaling=
             n -= take
 
     advance(W)
-    torch.cuda.synchronize()
-    per, wall = timed_repeats(lambda r: advance(K), K, device, dist_on, group)
-    R = len(per)
+    if dist_on:
+        torch.cuda.synchronize()
+    per, wall = timed_repeats(lambda done, n: advance(n), K, device, dist_on, group)
     advance((EPOCH_STEPS - state["pos"]) % EPOCH_STEPS)   # finish the epoch in flight (flush) before reading back
     if mode == "sharded":
         eng.k.check_status()
     else:
         st = eng.epoch_stats()
-        done = W + R * K
+        done = W + K
         assert st.step == done + (-done) % EPOCH_STEPS, (st.step, done)
         assert np.isfinite(st.loss) and 0.05 < st.loss < 1.4, st.loss
+        if rank == 0 and getattr(args, "dump_outputs", None):
+            dump_outputs(eng, st, args.dump_outputs)   # before the probe below trains the same engine further
 
     # ---- dominant kernel: its launch period from HIP events on the stream it runs on ------------------
     probe_s = probe_steps = None
@@ -1203,8 +1222,8 @@ def bench_mf(args, device, world, rank, dist_on, force_mode=None, force_scaling=
             "global_batch": b_local * world, "parallelism": parallelism,
             "rccl_world_size": world if dist_on else None,
             "epoch": f"{EPOCH_STEPS} steps = {EPOCH_STEPS * b_local * world} triples (SURVEY 8d C2: ~1M triples / epoch)",
-            "timed_region": "continuous training, epoch after epoch; a repeat = the next K steps, with everything "
-                            "that falls into them: per epoch one device shuffle + staging (sort of every batch by "
+            "timed_region": "continuous training, epoch after epoch; K steps in windows of consecutive steps, each "
+                            "with everything that falls into them: per epoch one device shuffle + staging (sort of every batch by "
                             "item, layout; runs on a side stream during the previous epoch) and one flush launch",
         },
         "roofline": {
@@ -1250,6 +1269,22 @@ def bench_mf(args, device, world, rank, dist_on, force_mode=None, force_scaling=
     return out
 
 
+def dump_outputs(eng, st, out_dir):
+    """`--dump-outputs DIR`: what the timed MF path hands its caller, for comparing two builds output for output.
+    The fused steps keep the state mid-rotation inside an epoch (include/hiprec.h: it must not be read there), so
+    this is taken once the epoch in flight at the end of the timed steps is finished, i.e. after exactly the steps
+    of `epoch_stats().step`: every tensor of the model's state_dict as DIR/<key>.npy (float32, 2.5 MB in all at
+    configs[1]) and DIR/stats.npy = [step, loss, reg, loss_sum, reg_sum] (float64; loss / reg of the last step,
+    the sums over its epoch).  The inputs are the same from run to run; the outputs are not bit for bit: the
+    scatter sums gradients with float atomics, and at Adam lr 0.05 two runs stay element-wise close through the
+    first epoch (W + K <= 245) and drift apart over many (the epoch's loss sums stay within ~1e-3)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for key, t in eng.model.state_dict().items():
+        np.save(os.path.join(out_dir, f"{key}.npy"), t.detach().to(torch.float32).cpu().numpy())
+    np.save(os.path.join(out_dir, "stats.npy"),
+            np.array([st.step, st.loss, st.reg, st.loss_sum, st.reg_sum], dtype=np.float64))
+
+
 def compact_line(out, keep=("value", "unit", "ms_per_step", "scaling", "n_gpus", "steps", "repeats")):
     """A named sub-record of the one JSON line: the headline fields of another measurement of the same run."""
     if out is None:
@@ -1284,7 +1319,7 @@ def bench_mf_multi_gpu(args, device, world, rank, group=None):
 
     rep = side(lambda: bench_mf(args, device, world, rank, True, force_mode="replicated", force_scaling="weak", group=group))
     c4args = copy.copy(args)
-    c4args.steps, c4args.warmup = min(args.steps, 50), min(args.warmup, 5)
+    c4args.steps, c4args.warmup = min(args.steps, 5 * 50), min(args.warmup, 5)
     c4 = side(lambda: bench_mf_c4_sharded(c4args, device, world, rank, group=group))
     if rank != 0:
         return None
@@ -1320,7 +1355,7 @@ def alt_single_gpu(args, device, only=None):
 
     def sub(**kw):
         a = copy.copy(args)
-        a.steps, a.warmup, a.no_cpu_baseline = min(args.steps, 50), min(args.warmup, 10), True
+        a.steps, a.warmup, a.no_cpu_baseline = min(args.steps, 5 * 50), min(args.warmup, 10), True
         for k, v in kw.items():
             setattr(a, k, v)
         return a
@@ -1445,6 +1480,9 @@ def parse_args(argv=None):
                     help="replicated mode: 'rccl' = the C epoch driver calls ncclAllReduce itself on the engine's own "
                          "communicator (falls back to torch.distributed if any rank cannot create one), 'torch' = "
                          "torch.distributed.all_reduce from the python step loop")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="mf on one GPU: after the timed steps write the trained parameters and step statistics as "
+                         "DIR/<name>.npy (same arguments -> same inputs, so two builds can be compared)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N>1: weak = every rank feeds a full batch (global batch N x B); strong = the reference's "
                          "batch split over the ranks (global batch = B, identical semantics to one GPU)")
@@ -1453,6 +1491,9 @@ def parse_args(argv=None):
 
 def main():
     args = parse_args()
+    if args.dump_outputs and (args.gpus != 1 or args.workload != "mf" or args.force_exchange
+                              or os.environ.get("HIPREC_BENCH_FORCE_SHARDED") == "1"):
+        raise SystemExit("--dump-outputs: only the single-GPU mf workload (bench_mf) writes its outputs")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)  # does not return
     world = int(os.environ.get("WORLD_SIZE", "1"))

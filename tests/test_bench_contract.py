@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run_bench(*args):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env["HIP_VISIBLE_DEVICES"] = "-1"   # these are the no-GPU paths: the same on a host that has GPUs
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True,
                           env=env, timeout=120)
 
@@ -28,15 +30,41 @@ def test_single_gpu_run_without_a_gpu_fails_loudly():
     assert out.returncode != 0 and "needs an MI355X" in out.stderr
 
 
+def test_dump_outputs_is_refused_where_it_is_not_written():
+    """--dump-outputs writes what the single-GPU MF path computed; elsewhere it is an error before any GPU work."""
+    out = run_bench("--workload", "ncf", "--dump-outputs", "unused")
+    assert out.returncode != 0 and "--dump-outputs" in out.stderr and "mf" in out.stderr
+
+
+def test_synthetic_inputs_are_the_same_from_run_to_run():
+    """The benchmark's inputs are a function of its arguments: seeded, nothing drawn from global state."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import torch
+
+    torch.manual_seed(12345)
+    a = bench.synth_triples(10000, seed=100)
+    torch.manual_seed(54321)
+    b = bench.synth_triples(10000, seed=100)
+    assert all(torch.equal(x, y) for x, y in zip(a, b))
+    assert not torch.equal(a[0], bench.synth_triples(10000, seed=101)[0])
+
+
 def test_repeat_and_byte_accounting():
     sys.path.insert(0, ROOT)
     import bench
 
-    assert bench.n_repeats(20) == 10 and bench.n_repeats(2000) == 5 and bench.n_repeats(1) == 200
-    per = [0.010, 0.012, 0.011, 0.030, 0.0105]
-    f = bench.timing_fields(per, sum(per), steps=10, units_per_step=4096, world=2)
-    assert f["repeats"] == 5 and f["timed_steps_total"] == 50
-    assert f["ms_per_step"] == pytest.approx(1.1) and f["value"] == pytest.approx(2 * 4096 * 10 / 0.011)
+    # --steps K times exactly K steps: up to 5 windows of >= 20 consecutive steps, at least one window
+    assert bench.n_repeats(20) == 1 and bench.n_repeats(2000) == 5 and bench.n_repeats(1) == 1
+    assert bench.n_repeats(60) == 3 and bench.n_repeats(100) == 5
+    assert bench.window_sizes(2000) == [400] * 5 and bench.window_sizes(7) == [7] and bench.window_sizes(63) == [21] * 3
+    for k in (1, 4, 19, 20, 41, 99, 101, 245, 2000, 2003):
+        sizes = bench.window_sizes(k)
+        assert sum(sizes) == k and max(sizes) - min(sizes) <= 1 and (len(sizes) == 1 or min(sizes) >= 20), (k, sizes)
+    per = [0.0010, 0.0012, 0.0011, 0.0030, 0.00105]     # seconds per step of each window
+    f = bench.timing_fields(per, 0.06, steps=50, units_per_step=4096, world=2)
+    assert f["repeats"] == 5 and f["timed_steps_total"] == 50 and f["wall_ms_per_step"] == pytest.approx(1.2)
+    assert f["ms_per_step"] == pytest.approx(1.1) and f["value"] == pytest.approx(2 * 4096 / 0.0011)
     # SURVEY 8(d): 1 584 B per triple at dim 64; dense Adam adds 28 P, RMSprop 20 P per step, SGD nothing
     P = (6040 + 3706) * 65 + 1
     assert bench.algorithmic_bytes_per_triple(64) == 1584 and bench.algorithmic_bytes_per_triple(128) == 3120
@@ -161,3 +189,39 @@ def test_single_gpu_line_carries_live_sub_records_of_the_other_configs():
         assert 0 < roof["frac"] < 1 and roof["kernel_us"] > 0 and roof["kernel_us_source"].startswith("HIP events")
         assert roof["model"] and roof["bound"] in ("hbm", "mfma")
     assert alt["mf_c4shard_sgd"]["ms_per_step_whole_epochs"] > 0 and alt["mf_c4shard_sgd"]["roofline"]["step_frac"] > 0
+
+
+@pytest.mark.gpu
+def test_single_gpu_line_times_exactly_the_steps_and_dumps_the_same_outputs(tmp_path):
+    """`--steps K` is the number of timed steps, and `--dump-outputs DIR` writes what the timed MF path hands its
+    caller: the parameters once the epoch in flight is finished, and its step statistics -- the same for two runs
+    with the same arguments, up to the order of the atomic gradient sums."""
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    device = torch.device("cuda:0")
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        args = bench.parse_args(["--steps", "60", "--warmup", "5", "--no-cpu-baseline", "--no-alt",
+                                 "--dump-outputs", str(d)])
+        line = bench.bench_mf(args, device, 1, 0, False)
+        assert line["steps"] == 60 and line["timed_steps_total"] == 60 and line["repeats"] == 3
+        assert line["value"] == pytest.approx(4096 / (line["ms_per_step"] * 1e-3), rel=1e-6)
+        dumps.append({p.stem: np.load(p) for p in d.glob("*.npy")})
+        assert sum(p.stat().st_size for p in d.glob("*.npy")) < 64 << 20
+    a, b = dumps
+    assert set(a) == {"user_emb.weight", "item_emb.weight", "user_bias.weight", "item_bias.weight", "global_bias",
+                      "stats"}
+    assert a["user_emb.weight"].shape == (bench.U, bench.D) and a["item_emb.weight"].shape == (bench.I, bench.D)
+    assert all(a[k].dtype == np.float32 for k in a if k != "stats") and a["stats"].dtype == np.float64
+    assert a["stats"][0] == bench.EPOCH_STEPS        # 5 + 60 steps, then the rest of that epoch
+    assert np.isfinite(a["stats"]).all() and 0.05 < a["stats"][1] < 1.4
+    assert a["stats"][0] == b["stats"][0] and a["stats"][1:] == pytest.approx(b["stats"][1:], rel=1e-4)
+    for k in a:
+        # atomic sums may round differently from run to run; Adam's first moves of a row are +-lr whatever the
+        # gradient's size, so a gradient that sums to ~0 may move its element the other way: rare, never many
+        off = np.abs(a[k] - b[k]) > 1e-4 * (1.0 + np.abs(a[k]))
+        assert off.mean() <= 1e-3, (k, int(off.sum()))
