@@ -1,6 +1,6 @@
 """bench.py — BPR-MF training throughput on MI355X (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--optimizer sgd|adam|rmsprop]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--optimizer sgd|adam|rmsprop] [--full]
                     [--workload mf|mf-c4|mf-c4shard|ncf|lightgcn|...] [--scaling weak|strong]
 
 A "step" is one pass of the hot path over one batch of B = 4096 synthetic (user, pos, neg) triples:
@@ -26,6 +26,12 @@ afterwards.
 
 `--dump-outputs DIR` writes, after the timed steps, what the timed path hands its caller: the model's parameters
 (and the step statistics) once the epoch in flight is finished, as DIR/<name>.npy (see dump_outputs).
+
+A plain run of the mf workload does only what its headline needs: set-up, the W warm-up and K timed steps, the dump
+if asked for, the JSON line.  `--full` adds, for the mf workload, what takes runs of its own: the dominant kernel's
+launch period and the roofline on it, the CPU baseline, and the sub-records of the other configurations (`alt`; at
+N > 1 also the same-run single-GPU step).  At N > 1 the sharded step's roofline is derived from the timed step and is
+there either way.  The other workloads are measured as before with or without `--full`.
 
 `python bench.py --gpus N` without a torch.distributed environment starts its own N ranks (a child
 torch.distributed.run on 127.0.0.1); under torchrun it uses RANK / LOCAL_RANK / WORLD_SIZE as
@@ -1164,9 +1170,9 @@ def bench_mf(args, device, world, rank, dist_on, force_mode=None, force_scaling=
         if rank == 0 and getattr(args, "dump_outputs", None):
             dump_outputs(eng, st, args.dump_outputs)   # before the probe below trains the same engine further
 
-    # ---- dominant kernel: its launch period from HIP events on the stream it runs on ------------------
+    # ---- dominant kernel (--full): its launch period from HIP events on the stream it runs on ----------
     probe_s = probe_steps = None
-    if rank == 0:
+    if rank == 0 and args.full:
         peng = eng if mode == "single" else make_engine(device, args.optimizer)
         fused = peng.fused_step and mode != "sharded"
         P = min(max(K, MIN_TIMED_STEPS), 2000)
@@ -1197,19 +1203,6 @@ def bench_mf(args, device, world, rank, dist_on, force_mode=None, force_scaling=
     if rank != 0:
         return None
     n_params = (U + I) * (D + 1) + 1
-    gs_bytes = algorithmic_bytes_per_triple(D) * B                     # gather / scatter rows of one batch
-    step_bytes = gs_bytes + optimizer_sweep_bytes(args.optimizer, n_params)   # SURVEY §8(d) for THIS optimizer
-    kind_id = {"sgd": 0, "adam": 1, "rmsprop": 2}[args.optimizer]
-    if fused:
-        dom_name = (f"mf_bpr_fused_kernel<1,{kind_id}> (gather + score + BPR grad + scatter + "
-                    f"{args.optimizer} update, 1 launch/step)")
-        dom_s = probe_s / (probe_steps + 1)      # P step launches + the sweep-only flush
-        dom_bytes = step_bytes
-        pmc_name = f"hiprec::mf_bpr_fused_kernel<1, {kind_id}, false>"
-    else:
-        dom_name = "mf_bpr_grad_kernel (gather + score + BPR grad + atomic scatter)"
-        dom_s, dom_bytes, pmc_name = k_mean, gs_bytes, "hiprec::mf_bpr_grad_kernel<1>"
-    traffic, traffic_src = traffic_from_profiles(pmc_name)
     out = {"metric": "training interactions/sec (BPR triples)", "unit": "triples/s"}
     out.update(timing_fields(per, wall, K, b_local, world))
     out.update({
@@ -1226,7 +1219,22 @@ def bench_mf(args, device, world, rank, dist_on, force_mode=None, force_scaling=
                             "with everything that falls into them: per epoch one device shuffle + staging (sort of every batch by "
                             "item, layout; runs on a side stream during the previous epoch) and one flush launch",
         },
-        "roofline": {
+    })
+    if args.full:
+        gs_bytes = algorithmic_bytes_per_triple(D) * B                     # gather / scatter rows of one batch
+        step_bytes = gs_bytes + optimizer_sweep_bytes(args.optimizer, n_params)   # SURVEY §8(d) for THIS optimizer
+        kind_id = {"sgd": 0, "adam": 1, "rmsprop": 2}[args.optimizer]
+        if fused:
+            dom_name = (f"mf_bpr_fused_kernel<1,{kind_id}> (gather + score + BPR grad + scatter + "
+                        f"{args.optimizer} update, 1 launch/step)")
+            dom_s = probe_s / (probe_steps + 1)      # P step launches + the sweep-only flush
+            dom_bytes = step_bytes
+            pmc_name = f"hiprec::mf_bpr_fused_kernel<1, {kind_id}, false>"
+        else:
+            dom_name = "mf_bpr_grad_kernel (gather + score + BPR grad + atomic scatter)"
+            dom_s, dom_bytes, pmc_name = k_mean, gs_bytes, "hiprec::mf_bpr_grad_kernel<1>"
+        traffic, traffic_src = traffic_from_profiles(pmc_name)
+        out["roofline"] = {
             "bound": "hbm", "kernel": dom_name,
             "achieved": dom_bytes / dom_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": dom_bytes / dom_s / 1e9 / HBM_PEAK_GBS,
@@ -1242,8 +1250,7 @@ def bench_mf(args, device, world, rank, dist_on, force_mode=None, force_scaling=
             # whole step, per GPU: (triples/s) x (row bytes per triple + this optimizer's sweep bytes per triple)
             "step_frac": out["value"] / world * (algorithmic_bytes_per_triple(D) + (step_bytes - gs_bytes) / b_local)
                          / (HBM_PEAK_GBS * 1e9),
-        },
-    })
+        }
     if exchange is not None:
         step_s = out["ms_per_step"] * 1e-3
         out["config"].update({k: round(v) for k, v in exchange.items()})
@@ -1264,7 +1271,7 @@ def bench_mf(args, device, world, rank, dist_on, force_mode=None, force_scaling=
                                                      f"triples/GPU + this shard's dense {args.optimizer} sweep",
                            "kernel_us": step_s * 1e6, "kernel_us_source": "the timed step itself (HIP events)",
                            "traffic": None, "traffic_source": None}
-    if not args.no_cpu_baseline and world == 1:  # the CPU leg is timed on rank 0 at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg is timed on rank 0 at N = 1 only
         out["cpu_baseline"] = cpu_baseline(args.optimizer)
     return out
 
@@ -1304,10 +1311,13 @@ def bench_mf_multi_gpu(args, device, world, rank, group=None):
     own batch (global batch 4096 split over the ranks: `scaling: strong`, the single-GPU step's semantics) -- and the
     two other N-GPU forms this repo has ride along as named sub-records: `alt.replicated` (data-parallel replicas of
     the 2.5 MB tables, one all-reduce per step, weak scaling) and `alt.c4_sharded` (BASELINE configs[3], 10 M x 1 M x
-    128 row-sharded, 65 536 triples per GPU and step).  One JSON line."""
+    128 row-sharded, 65 536 triples per GPU and step).  The sub-records and the same-run single-GPU step are
+    measured with `--full` only.  One JSON line."""
     import copy
 
     out = bench_mf(args, device, world, rank, True, force_mode="sharded", force_scaling="strong", group=group)
+    if not args.full:
+        return out
 
     def side(fn):
         # a sub-record must not cost the run its headline: an error in one (the same code and shapes run on every
@@ -1342,8 +1352,8 @@ ALT_WORKLOADS = ("ncf", "mf_c4shard_sgd", "mf_c4shard_adam", "mf_c4_adam_fullcov
 
 
 def alt_single_gpu(args, device, only=None):
-    """The other BASELINE.json configs under the SAME clock as the headline: the stock
-    `python bench.py --gpus 1 --steps K --warmup W` keeps configs[1] as its line and carries, as `alt`, one sub-record
+    """The other BASELINE.json configs under the SAME clock as the headline:
+    `python bench.py --gpus 1 --steps K --warmup W --full` keeps configs[1] as its line and carries, as `alt`, one sub-record
     per remaining config measured LIVE in this process -- `ncf` (configs[2], emb_dim 32), `mf_c4shard_sgd` /
     `mf_c4shard_adam` (one rank's share of configs[3]; SGD as owner pulls, Adam as the exact lazy form),
     `mf_c4_adam_fullcov` (configs[3] WHOLE on this GPU with the reference's default optimizer, every row met in every
@@ -1424,11 +1434,17 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--optimizer", default="adam", choices=["sgd", "adam", "rmsprop"],
                     help="mf: adam is the reference's own default (configs/mf_default.json); sgd / rmsprop are the other two torch_engine.py:23-39 builds")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="mf: also measure what the headline does not need (dominant kernel + roofline, CPU baseline, "
+                         "the `alt` sub-records); a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="skip the CPU baseline (for the mf workload it is only taken with --full)")
     ap.add_argument("--no-alt", action="store_true",
-                    help="mf at --gpus 1: skip the `alt` sub-records (the other BASELINE configs measured in the same run)")
+                    help="mf at --gpus 1 with --full: skip the `alt` sub-records (the other BASELINE configs measured "
+                         "in the same run)")
     ap.add_argument("--alt-only", default=None,
-                    help="mf at --gpus 1: comma-separated subset of the `alt` sub-records (%s)" % ", ".join(ALT_WORKLOADS))
+                    help="mf at --gpus 1 with --full: comma-separated subset of the `alt` sub-records (%s)"
+                         % ", ".join(ALT_WORKLOADS))
     ap.add_argument("--two-kernel", action="store_true",
                     help="mf: gradient kernel + dense optimizer sweep per step instead of the fused one-kernel step")
     ap.add_argument("--workload", default="mf", choices=["mf", "ncf", "lightgcn", "mf-c4shard", "mf-c4", "pgmf", "t2v", "ngcf"],
@@ -1542,7 +1558,7 @@ def main():
         out = bench_mf_multi_gpu(args, device, world, rank)
     else:
         out = bench_mf(args, device, world, rank, dist_on)
-        if not dist_on and out is not None and not args.no_alt and not args.two_kernel:
+        if not dist_on and out is not None and args.full and not args.no_alt and not args.two_kernel:
             out["alt"] = alt_single_gpu(args, device, only=args.alt_only.split(",") if args.alt_only else None)
     if dist_on and args.workload in ("pgmf", "t2v", "ngcf"):
         raise SystemExit(f"--workload {args.workload} is single-GPU (no data-parallel wrapper)")

@@ -124,7 +124,7 @@ def test_gpus_n_line_is_the_row_sharded_split_with_the_other_forms_as_sub_record
     import bench
     from loopback import VirtualWorld
 
-    args = bench.parse_args(["--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"])
+    args = bench.parse_args(["--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--full"])
     device = torch.device("cuda:0")
     world = VirtualWorld(2, timeout=120.0)
     try:
@@ -164,6 +164,41 @@ def test_alt_records_are_the_remaining_baseline_configs():
     assert bench.ALT_WORKLOADS == ("ncf", "mf_c4shard_sgd", "mf_c4shard_adam", "mf_c4_adam_fullcov", "lightgcn")
     args = bench.parse_args([])
     assert args.no_alt is False and args.alt_only is None and bench.parse_args(["--no-alt"]).no_alt is True
+    # the sub-records, like the CPU baseline and the roofline probe, are taken with --full only
+    assert args.full is False and bench.parse_args(["--full"]).full is True
+
+
+@pytest.mark.gpu
+def test_plain_single_gpu_run_prints_the_headline_only():
+    """`python bench.py --gpus 1 --steps K --warmup W` sets up, warms up, times the K steps and prints its one line:
+    the headline fields, and nothing that takes runs of its own (no roofline probe, CPU baseline or sub-records)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "5"],
+                         capture_output=True, text=True, env=env, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, out.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["metric"] == "training interactions/sec (BPR triples)" and line["unit"] == "triples/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["steps"] == 40 and line["warmup"] == 5 and line["timed_steps_total"] == 40 and line["repeats"] == 2
+    assert line["value"] == pytest.approx(4096 / (line["ms_per_step"] * 1e-3), rel=1e-6)
+    assert not {"roofline", "cpu_baseline", "alt"} & set(line), sorted(line)
+
+
+@pytest.mark.gpu
+def test_full_single_gpu_line_carries_the_roofline_probe():
+    """--full: the dominant kernel's launch period, timed with HIP events after the timed steps, and the roofline on it."""
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    args = bench.parse_args(["--steps", "40", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-alt"])
+    line = bench.bench_mf(args, torch.device("cuda:0"), 1, 0, False)
+    roof = line["roofline"]
+    assert roof["kernel_us"] > 0 and roof["grad_only_kernel_us"] > 0 and 0 < roof["frac"] < 1
+    assert roof["kernel_us_source"].startswith("HIP events") and "cpu_baseline" not in line
 
 
 @pytest.mark.gpu

@@ -45,20 +45,20 @@ for G in $EV_GROUPS; do
 case $G in
 mf)   # BASELINE configs[1], the headline (+ the replicated data-parallel step at world 1)
   stamp mf
-  prof adam --steps 500 --warmup 50
-  prof adam_20 --steps 20 --warmup 5
-  prof sgd --optimizer sgd --steps 500 --warmup 50
-  pmc adam --steps 200 --warmup 20
-  pmc sgd --optimizer sgd --steps 200 --warmup 20
+  prof adam --full --steps 500 --warmup 50
+  prof adam_20 --full --steps 20 --warmup 5
+  prof sgd --full --optimizer sgd --steps 500 --warmup 50
+  pmc adam --full --steps 200 --warmup 20
+  pmc sgd --full --optimizer sgd --steps 200 --warmup 20
   collect
-  line adam_20 200 --steps 20 --warmup 5
-  line adam 200
-  for o in sgd rmsprop; do line $o 200 --optimizer $o --no-cpu-baseline; done
+  line adam_20 200 --full --steps 20 --warmup 5
+  line adam 200 --full
+  for o in sgd rmsprop; do line $o 200 --full --optimizer $o --no-cpu-baseline; done
   # `bench.py --gpus N` as the driver runs it, at world size 1: the row-sharded split as the headline, the replicated
-  # and the configs[3] forms as sub-records
-  sharded_line multi_w1 300 --steps 200
-  sharded_line multi_w1_20 300 --steps 20 --warmup 5
-  sharded_line multi_w1_torch 300 --steps 200 --dp-collective torch
+  # and the configs[3] forms as sub-records (--full)
+  sharded_line multi_w1 300 --full --steps 200
+  sharded_line multi_w1_20 300 --full --steps 20 --warmup 5
+  sharded_line multi_w1_torch 300 --full --steps 200 --dp-collective torch
   ;;
 c4)   # BASELINE configs[3] on one GPU: one rank's shard and the whole table; SGD (owner pulls) and exact lazy Adam / RMSprop
   stamp c4
