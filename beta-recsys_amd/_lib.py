@@ -113,6 +113,21 @@ class PgmfTables(Structure):
                 ("n_users", c_int64), ("n_items", c_int64), ("dim", c_int32), ("_pad", c_int32)]
 
 
+class UltraGcnTables(Structure):
+    """hiprec_ultragcn_tables (include/hiprec.h)."""
+
+    _fields_ = [("user_embeds", c_void_p), ("item_embeds", c_void_p), ("n_users", c_int64), ("n_items", c_int64),
+                ("dim", c_int32), ("_pad", c_int32)]
+
+
+class UltraGcnParams(Structure):
+    """hiprec_ultragcn_params (include/hiprec.h)."""
+
+    _fields_ = [("beta_u", c_void_p), ("beta_i", c_void_p), ("ii_neighbor", c_void_p), ("ii_sim", c_void_p),
+                ("n_neighbors", c_int32), ("w1", c_float), ("w2", c_float), ("w3", c_float), ("w4", c_float),
+                ("negative_weight", c_float), ("gamma", c_float), ("lambda_", c_float)]
+
+
 class T2vTables(Structure):
     """hiprec_t2v_tables (include/hiprec.h)."""
 
@@ -326,6 +341,25 @@ SIGNATURES = {
          c_size_t, _P],
     ),
     "hiprec_t2v_predict": (c_int, [POINTER(T2vTables), _P, _P, c_int64, _P, _P, _P]),
+    "hiprec_sumsq_workspace_bytes": (c_size_t, []),
+    "hiprec_sumsq": (c_int, [_P, c_int64, _P, c_size_t, _P]),
+    "hiprec_opt_dense_step_decay": (
+        c_int,
+        [c_int, _P, _P, _P, _P, c_int64, c_double, c_double, c_double, c_double, _P, _P, c_float, _P, c_size_t, _P],
+    ),
+    "hiprec_decay_grad": (c_int, [_P, _P, c_int64, c_float, _P]),
+    "hiprec_ultragcn_grad": (
+        c_int,
+        [POINTER(UltraGcnTables), POINTER(UltraGcnTables), POINTER(UltraGcnParams), _P, _P, _P, c_int64, c_int32, _P,
+         _P, _P, c_size_t, _P],
+    ),
+    "hiprec_ultragcn_predict": (c_int, [POINTER(UltraGcnTables), _P, _P, c_int64, _P, _P, _P]),
+    "hiprec_ultragcn_epoch": (
+        c_int,
+        [POINTER(UltraGcnTables), POINTER(UltraGcnTables), POINTER(UltraGcnParams), _P, _P, _P, c_int64, c_int64,
+         c_int32, c_int, c_double, c_double, c_double, c_double, _P, _P, _P, _P, c_int64, _P, c_size_t, _P, _P,
+         c_size_t, _P],
+    ),
     "hiprec_alias_sample": (c_int, [_P, _P, _P, c_int64, ctypes.c_uint64, _P, c_int64, _P]),
     "hiprec_ngcf_plan_bytes": (c_size_t, []),
     "hiprec_ngcf_forward": (c_int, [POINTER(NgcfPlan), c_int, _P]),

@@ -1251,6 +1251,81 @@ int hiprec_ngcf_grad(const hiprec_ngcf_plan* plan, const int64_t* users, const i
                      const int64_t* neg, int64_t batch, float inv_batch, hiprec_stats* stats,
                      void* scratch, size_t scratch_bytes, void* stream);
 
+/* ================= UltraGCN (models/ultragcn.py: two tables, weighted BCE over 1 + N items, K-neighbour constraint) ====
+ * The host keeps [user_embeds | item_embeds] in ONE flat buffer in that order (and the dense gradient in another). */
+typedef struct hiprec_ultragcn_tables {
+  float* user_embeds; /* [n_users, dim] */
+  float* item_embeds; /* [n_items, dim] */
+  int64_t n_users;
+  int64_t n_items;
+  int32_t dim;        /* <= 256 */
+  int32_t _pad;
+} hiprec_ultragcn_tables;
+
+/* What UltraGCN.__init__ (ultragcn.py:36-68) fixes for the whole run.  beta_u / beta_i are constraint_mat's fp32 vectors
+ * (data/base_data.py:410-431); ii_neighbor / ii_sim the two [n_items, n_neighbors] tables of get_ii_constraint_mat
+ * (ultragcn.py:9-33; may be NULL when n_neighbors == 0 or lambda_ == 0, which skips the constraint term).  w2 must be
+ * > 0 (the reference raises NameError otherwise); w4 <= 0 makes every negative weight the constant w3. */
+typedef struct hiprec_ultragcn_params {
+  const float* beta_u;        /* [n_users] */
+  const float* beta_i;        /* [n_items] */
+  const int64_t* ii_neighbor; /* [n_items, n_neighbors] */
+  const float* ii_sim;        /* [n_items, n_neighbors] */
+  int32_t n_neighbors;
+  float w1, w2, w3, w4;
+  float negative_weight;
+  float gamma;
+  float lambda_;
+} hiprec_ultragcn_params;
+
+/* ---- sum of squares of n floats as per-block fp64 partials: workspace[0] = number of partials, workspace[1 + b] =
+ * block b's sum (hiprec_sumsq_workspace_bytes() of device memory).  The loss value of UltraGCN's gamma term needs
+ * sum w^2 of the weights a step STARTS from: hiprec_opt_dense_step_decay leaves it behind for the next step in this
+ * layout, this call computes it when the weights came from elsewhere (construction, load_state_dict, resume). */
+size_t hiprec_sumsq_workspace_bytes(void);
+int hiprec_sumsq(const float* x, int64_t n, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- hiprec_opt_dense_step for a loss that carries decay / 2 * sum w^2 over EVERY element (ultragcn.py:153-162): each
+ * element's gradient is g + decay * w, formed in the sweep (no pass of its own over the tables), and the sweep leaves the
+ * sums of squares of the UPDATED weights in sumsq_workspace (layout of hiprec_sumsq).  When the status word of `stats` is
+ * raised (an id out of range in the preceding *_grad call) the sweep changes nothing. */
+int hiprec_opt_dense_step_decay(int kind, float* w, float* g, float* m, float* v, int64_t n, double lr, double beta1,
+                                double beta2, double eps, hiprec_stats* stats, const void* scratch, float decay,
+                                void* sumsq_workspace, size_t sumsq_workspace_bytes, void* stream);
+
+/* ---- g[0:n] += gamma * w[0:n]: the gamma term's gradient written out, for callers that want the whole gradient in
+ * memory (backward_only); a training step never needs it. */
+int hiprec_decay_grad(float* g, const float* w, int64_t n, float gamma, void* stream);
+
+/* ---- zero_grad + forward + loss + backward of UltraGCNEngine.train_single_batch (ultragcn.py:196-216) without the
+ * gamma term's gradient (hiprec_opt_dense_step_decay adds it): users[batch], pos[batch], neg[batch * n_neg] row-major,
+ * n_neg >= 1.  loss = sum_b [ wp bce(s(u,p), 1) + negative_weight mean_n(wn bce(s(u,n), 0)) ]
+ *        + gamma / 2 * sum w^2 (from sumsq_workspace; may be NULL when gamma == 0)
+ *        + lambda_ * sum_b sum_k -sim[p,k] log sigmoid(s(u, nbr[p,k])).
+ * Accumulates into the dense gradient g, leaves the loss partials in scratch and advances the step counter.  A sample
+ * whose user or positive is out of range is skipped, as is a negative / neighbour term with such an id; the status
+ * bits are set. */
+int hiprec_ultragcn_grad(const hiprec_ultragcn_tables* w, const hiprec_ultragcn_tables* g,
+                         const hiprec_ultragcn_params* params, const int64_t* users, const int64_t* pos,
+                         const int64_t* neg, int64_t batch, int32_t n_neg, const void* sumsq_workspace,
+                         hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- scores[k] = <U[u_k], V[i_k]>  (UltraGCN.predict, ultragcn.py:167-179) */
+int hiprec_ultragcn_predict(const hiprec_ultragcn_tables* w, const int64_t* users, const int64_t* items, int64_t n,
+                            float* scores, hiprec_stats* stats, void* stream);
+
+/* ---- UltraGCNEngine.train_an_epoch (ultragcn.py:218-236) over resident arrays in visiting order (users / pos
+ * [n_samples], neg [n_samples * n_neg], last batch short): per batch hiprec_ultragcn_grad and
+ * hiprec_opt_dense_step_decay over the flat buffers that w / g point into, enqueued back to back.  hiprec_sumsq
+ * over flat_w runs once at the start (the weights may have been replaced since the last sweep); after that every sweep
+ * hands the sums of its new weights to the next step. */
+int hiprec_ultragcn_epoch(const hiprec_ultragcn_tables* w, const hiprec_ultragcn_tables* g,
+                          const hiprec_ultragcn_params* params, const int64_t* users, const int64_t* pos,
+                          const int64_t* neg, int64_t n_samples, int64_t batch, int32_t n_neg, int kind, double lr,
+                          double beta1, double beta2, double eps, float* flat_w, float* flat_g, float* flat_m,
+                          float* flat_v, int64_t n_flat, void* sumsq_workspace, size_t sumsq_workspace_bytes,
+                          hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
