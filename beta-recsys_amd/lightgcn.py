@@ -20,9 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .mf import _new_stats, raise_on_status, read_stats
-from .ncf import _FlatModel, _ParamView
-from .flat_engine import FlatModelEngine
+from .flat_engine import FlatModelEngine, _FlatModel, _ParamView, index_tensor
 
 
 def _slice_rows(rowptr, col, val, n, nnz):
@@ -543,21 +541,15 @@ class LightGCN(_FlatModel):
         self._staged_for = None              # the propagation below overwrites what an optimizer launch may have staged
         lib = self._require_hip()
         dev = self._flat.device
-        users_t, items_t = (x.to(dev, torch.int64).reshape(-1).contiguous() if torch.is_tensor(x) else
-                            torch.as_tensor(np.asarray(x), dtype=torch.int64).to(dev).reshape(-1).contiguous()
-                            for x in (users, items))
-        if self._stats is None or self._stats.device != dev:
-            self._stats = _new_stats(dev)
+        users_t, items_t = index_tensor(users, dev), index_tensor(items, dev)
+        stats = self._device_stats()
         plan = self.plan()
         st = _lib.stream_ptr(dev)
         _lib.check(lib.hiprec_lightgcn_propagate(ctypes.byref(plan), None, 1.0, st))
         scores = torch.empty(users_t.numel(), dtype=torch.float32, device=dev)
         _lib.check(lib.hiprec_lightgcn_predict(ctypes.byref(plan), _lib.ptr(users_t), _lib.ptr(items_t),
-                                               users_t.numel(), _lib.ptr(scores), _lib.ptr(self._stats), st))
-        s = read_stats(self._stats)
-        if s.status:
-            self._stats = None
-            raise_on_status(s.status)
+                                               users_t.numel(), _lib.ptr(scores), _lib.ptr(stats), st))
+        self._check_status()
         return scores
 
 
@@ -577,8 +569,7 @@ class LightGCNEngine(FlatModelEngine):
         lib = self._setup()
         m = self.model
         dev = m.flat.device
-        users, pos, neg = (torch.as_tensor(x, device=dev).to(torch.int64).reshape(-1).contiguous()
-                           for x in batch_data)
+        users, pos, neg = (index_tensor(x, dev) for x in batch_data)
         B = users.numel()
         if not (pos.numel() == B and neg.numel() == B):
             raise ValueError("batch tensors differ in length")
@@ -619,12 +610,6 @@ class LightGCNEngine(FlatModelEngine):
     def train_an_epoch(self, train_loader, epoch_id):
         """lightgcn.py:154-169: prints the last batch's loss, logs the epoch sum."""
         assert hasattr(self, "model"), "Please specify the exact model !"
-        self.model.train()
-        lib = self._setup()
-        _lib.check(lib.hiprec_stats_begin_epoch(_lib.ptr(self._stats),
-                                                _lib.stream_ptr(self.model.flat.device)))
-        for batch_data in train_loader:
-            self._enqueue_step(batch_data)
-        st = self._sync_stats()
+        st = self._run_epoch(train_loader)
         print("[Training Epoch {}], Loss {}".format(epoch_id, st.loss))
         self.writer.add_scalar("model/loss", st.loss_sum, epoch_id)

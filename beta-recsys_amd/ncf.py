@@ -18,79 +18,12 @@ CPU draws replayed (same torch seed -> the reference's masks) or drawn on the de
 import ctypes
 import os
 
-import numpy as np
 import torch
 import torch.nn as nn
-from torch.nn import Parameter
 
 from . import _lib
-from .mf import _new_stats, clear_status, raise_on_status, read_stats, timeit
-from .torch_engine import ModelEngine
-
-
-class _ParamView(nn.Module):
-    """A module whose parameters (``weight`` and optionally ``bias``) are views of a flat buffer."""
-
-    def __init__(self, weight, bias=None):
-        super().__init__()
-        self.weight = Parameter(weight, requires_grad=False)
-        if bias is not None:
-            self.bias = Parameter(bias, requires_grad=False)
-
-    def extra_repr(self):
-        return "x".join(str(s) for s in self.weight.shape)
-
-
-class _FlatModel(nn.Module):
-    """Base: named parameter views over ONE flat fp32 buffer (tables first, dense layers after)."""
-
-    def _build(self, spec):
-        """spec: list of (name, shape); allocates the flat buffer and returns the views by name."""
-        self._spec = [(n, tuple(s)) for n, s in spec]
-        sizes = [int(np.prod(s)) for _, s in self._spec]
-        self._offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        self._flat = torch.zeros(int(self._offsets[-1]), dtype=torch.float32)
-        return self.views()
-
-    def views(self, flat=None):
-        flat = self._flat if flat is None else flat
-        return {n: flat[self._offsets[k]:self._offsets[k + 1]].view(*s)
-                for k, (n, s) in enumerate(self._spec)}
-
-    def offset_of(self, name):
-        return int(self._offsets[[n for n, _ in self._spec].index(name)])
-
-    def _owner(self, name):
-        mod = self
-        parts = name.split(".")
-        for p in parts[:-1]:
-            mod = getattr(mod, p) if not p.isdigit() else mod[int(p)]
-        return mod, parts[-1]
-
-    def _rebind(self, flat):
-        self._flat = flat
-        for name, view in self.views(flat).items():
-            mod, attr = self._owner(name)
-            getattr(mod, attr).data = view
-
-    def _apply(self, fn, recurse=True):
-        new_flat = fn(self._flat)
-        if new_flat.dtype != torch.float32:
-            raise TypeError("hiprec models keep fp32 parameters (the reference trains in fp32)")
-        if new_flat is not self._flat:
-            self._rebind(new_flat.contiguous())
-        return self
-
-    @property
-    def flat(self):
-        return self._flat
-
-    def _require_hip(self):
-        if self._flat.device.type != "cuda":
-            raise RuntimeError(
-                "hiprec NCF models compute on an MI355X through libhiprec.so only; parameters are "
-                f"on {self._flat.device} and there is deliberately no CPU fallback")
-        return _lib.load()
+from .flat_engine import FlatModelEngine, _FlatModel, _ParamView, index_tensor
+from .mf import timeit
 
 
 def _tower_dims(emb_dim, n_layers):
@@ -116,7 +49,6 @@ class _NcfBase(_FlatModel):
         self.config = config
         self._plan_cache = None
         self._ws = None
-        self._stats = None
 
     # -- plan / workspace ---------------------------------------------------------------------
     def _names(self):
@@ -238,30 +170,22 @@ class _NcfBase(_FlatModel):
         """models/ncf.py:52-71 / gmf.py:29-36 / mlp.py:40-51 without autograd: [n, 1] ratings."""
         lib = self._require_hip()
         dev = self._flat.device
-        users = torch.as_tensor(user_indices, device=dev).to(torch.int64).reshape(-1).contiguous()
-        items = torch.as_tensor(item_indices, device=dev).to(torch.int64).reshape(-1).contiguous()
+        users, items = index_tensor(user_indices, dev), index_tensor(item_indices, dev)
         if users.numel() != items.numel():
             raise ValueError("user_indices and item_indices must have the same length")
         n = users.numel()
-        if self._stats is None or self._stats.device != dev:
-            self._stats = _new_stats(dev)
+        stats = self._device_stats()
         plan = self.plan(max(n, 1))
         if n:
             self.draw_keep_masks(plan, n)   # like the reference, dropout follows self.training here too
         _lib.check(lib.hiprec_ncf_forward(ctypes.byref(plan), _lib.ptr(users), _lib.ptr(items), n,
-                                          _lib.ptr(self._stats), _lib.stream_ptr(dev)))
+                                          _lib.ptr(stats), _lib.stream_ptr(dev)))
         return self._ws["scores"][:n].clone().view(n, 1)
 
     def predict(self, user_indices, item_indices):
         """models/ncf.py:73-78: numpy / list ids in, [n, 1] score tensor on the device out."""
-        dev = self._flat.device
-        u = torch.as_tensor(np.asarray(user_indices), dtype=torch.int64).to(dev)
-        i = torch.as_tensor(np.asarray(item_indices), dtype=torch.int64).to(dev)
-        scores = self.forward(u, i)
-        st = read_stats(self._stats)
-        if st.status:
-            self._stats = None
-            raise_on_status(st.status)
+        scores = self.forward(user_indices, item_indices)
+        self._check_status()
         return scores
 
     def init_weight(self):
@@ -385,33 +309,16 @@ def _init_linear_like_torch(weight, bias):
     nn.init.uniform_(bias, -bound, bound)
 
 
-class _NcfEngine(ModelEngine):
-    """Shared engine: BCE step through hiprec_ncf_grad + one dense optimizer sweep."""
+class _NcfEngine(FlatModelEngine):
+    """Shared engine: BCE step through the one call hiprec_ncf_step (gradient + dense optimizer sweep)."""
 
     print_last_loss = False  # NeuMFEngine prints the last batch's loss, GMF/MLP the epoch sum
-
-    def _post_init(self):
-        self.model.to(self.device)
-        self._ready = False
-
-    def _setup(self):
-        lib = self.require_hip()
-        flat = self.model.flat
-        if self._ready and self._g_flat.device == flat.device:
-            return lib
-        self._g_flat = torch.zeros_like(flat)
-        self.optimizer.allocate_state(flat)
-        self._scratch = torch.zeros(lib.hiprec_scratch_bytes(0), dtype=torch.uint8, device=flat.device)
-        self._stats = _new_stats(flat.device, self.optimizer.beta1 or 0.9, self.optimizer.beta2 or 0.999)
-        self._ready = True
-        return lib
 
     def _enqueue_step(self, users, items, ratings):
         lib = self._setup()
         m, opt = self.model, self.optimizer
         dev = m.flat.device
-        users = torch.as_tensor(users, device=dev).to(torch.int64).reshape(-1).contiguous()
-        items = torch.as_tensor(items, device=dev).to(torch.int64).reshape(-1).contiguous()
+        users, items = index_tensor(users, dev), index_tensor(items, dev)
         ratings = torch.as_tensor(ratings, device=dev).to(torch.float32).reshape(-1).contiguous()
         B = users.numel()
         if not (items.numel() == B and ratings.numel() == B):
@@ -429,53 +336,25 @@ class _NcfEngine(ModelEngine):
             m.table_floats(), m.offset_of("affine_output.bias"), opt.lr, opt.beta1, opt.beta2, opt.eps,
             _lib.ptr(self._stats), _lib.ptr(self._scratch), self._scratch.numel(), st))
 
-    def _sync_stats(self):
-        st = read_stats(self._stats)
-        if st.status:
-            clear_status(self._stats)
-            raise_on_status(st.status)
-        return st
+    def _epoch_step(self, batch):
+        self._enqueue_step(batch[0], batch[1], torch.as_tensor(batch[2]).float())
 
     def backward_only(self, users, items, ratings):
         """zero_grad + forward + backward without the optimizer step: ``(loss, grads dict)``."""
         lib = self._setup()
         m = self.model
         dev = m.flat.device
-        users = torch.as_tensor(users, device=dev).to(torch.int64).contiguous()
-        items = torch.as_tensor(items, device=dev).to(torch.int64).contiguous()
+        users, items = index_tensor(users, dev), index_tensor(items, dev)
         ratings = torch.as_tensor(ratings, device=dev).to(torch.float32).contiguous()
         B = users.numel()
-        st = _lib.stream_ptr(dev)
         plan = m.plan(B, self._g_flat)
         m.draw_keep_masks(plan, B)
         _lib.check(lib.hiprec_ncf_grad(
             ctypes.byref(plan), _lib.ptr(users), _lib.ptr(items), _lib.ptr(ratings), B, 1.0 / B,
-            _lib.ptr(self._stats), _lib.ptr(self._scratch), self._scratch.numel(), st))
-        g = m.views(self._g_flat)
-        _lib.check(lib.hiprec_finalize_stats(_lib.ptr(self._stats), _lib.ptr(self._scratch),
-                                             _lib.ptr(g["affine_output.bias"]), None, st))
-        stt = self._sync_stats()
-        grads = {k: v.clone() for k, v in g.items()}
-        self._g_flat.zero_()
-        return stt.loss, grads
-
-    def load_optimizer_state(self, step, exp_avg=None, exp_avg_sq=None):
-        """Restore the optimizer clock and moments (dicts keyed like ``state_dict``)."""
-        lib = self._setup()
-        opt, m = self.optimizer, self.model
-        dev = m.flat.device
-        _lib.check(lib.hiprec_stats_reset(_lib.ptr(self._stats), opt.beta1 or 0.9, opt.beta2 or 0.999,
-                                          _lib.stream_ptr(dev)))
-        _lib.check(lib.hiprec_stats_set_step(_lib.ptr(self._stats), int(step), opt.beta1 or 0.9,
-                                             opt.beta2 or 0.999, _lib.stream_ptr(dev)))
-        for buf, src in ((opt.exp_avg, exp_avg), (opt.exp_avg_sq, exp_avg_sq)):
-            if buf is None:
-                continue
-            if src is None:
-                buf.zero_()
-                continue
-            for name, view in m.views(buf).items():
-                view.copy_(torch.as_tensor(src[name], dtype=torch.float32).reshape(view.shape))
+            _lib.ptr(self._stats), _lib.ptr(self._scratch), self._scratch.numel(), _lib.stream_ptr(dev)))
+        # d loss / d affine_output.bias travels in the scratch partials: the shared finish writes it into its slot
+        st, grads = self._finish_backward_only(_lib.ptr(m.views(self._g_flat)["affine_output.bias"]))
+        return st.loss, grads
 
     def train_single_batch(self, users, items, ratings):
         """models/ncf.py:100-120: one optimisation step, returns the batch loss as a float."""
@@ -487,14 +366,7 @@ class _NcfEngine(ModelEngine):
     def train_an_epoch(self, train_loader, epoch_id):
         """models/ncf.py:122-140 (gmf.py:82-100, mlp.py:98-116): one host sync per epoch."""
         assert hasattr(self, "model"), "Please specify the exact model !"
-        self.model.train()
-        lib = self._setup()
-        _lib.check(lib.hiprec_stats_begin_epoch(_lib.ptr(self._stats),
-                                                _lib.stream_ptr(self.model.flat.device)))
-        for batch_id, batch in enumerate(train_loader):
-            user, item, rating = batch[0], batch[1], batch[2]
-            self._enqueue_step(user, item, torch.as_tensor(rating).float())
-        st = self._sync_stats()
+        st = self._run_epoch(train_loader)
         shown = st.loss if self.print_last_loss else st.loss_sum
         print("[Training Epoch {}], Loss {}".format(epoch_id, shown))
         self.writer.add_scalar("model/loss", st.loss_sum, epoch_id)
@@ -515,7 +387,6 @@ class NeuMFEngine(_NcfEngine):
             self.load_pretrain_weights()
         else:
             self.init_weights()
-        self._post_init()
 
     def init_weights(self):
         """models/ncf.py:142-153, quirk Q8 included: ``embedding_user_mlp`` is initialised twice and
@@ -568,7 +439,6 @@ class GMFEngine(_NcfEngine):
         self.model = GMF(config["model"])
         self.loss = torch.nn.BCELoss()
         super(GMFEngine, self).__init__(config)
-        self._post_init()
 
 
 class MLPEngine(_NcfEngine):
@@ -578,4 +448,3 @@ class MLPEngine(_NcfEngine):
         self.model = MLP(config["model"])
         self.loss = torch.nn.BCELoss()
         super(MLPEngine, self).__init__(config)
-        self._post_init()

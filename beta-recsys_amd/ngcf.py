@@ -17,15 +17,13 @@ draws — the same seed drops the same messages as the reference (pinned by the 
 """
 import ctypes
 
-import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _lib
+from .flat_engine import FlatModelEngine, _FlatModel, _ParamView, index_tensor
 from .lightgcn import _csr_from_coo, _slice_rows, build_sliced_graphs
-from .mf import _new_stats, raise_on_status, read_stats
-from .ncf import _FlatModel, _init_linear_like_torch, _ParamView
-from .flat_engine import FlatModelEngine
+from .ncf import _init_linear_like_torch
 
 
 class NGCF(_FlatModel):
@@ -71,7 +69,6 @@ class NGCF(_FlatModel):
         self.dropout_seed = int(config["dropout_seed"]) if "dropout_seed" in config else 0
         self._graph = None
         self._ws = None
-        self._stats = None
         self._step = 0
 
     # ---- graph + workspace ------------------------------------------------------------------------
@@ -196,12 +193,6 @@ class NGCF(_FlatModel):
             out.append(buf)
         return out
 
-    def _device_stats(self):
-        dev = self._flat.device
-        if self._stats is None or self._stats.device != dev:
-            self._stats = _new_stats(dev)
-        return self._stats
-
     # ---- reference API ----------------------------------------------------------------------------
     def forward(self, norm_adj=None):
         """ngcf.py:48-80 without autograd: ``(u_g_embeddings, i_g_embeddings)``, each ``[*, sum dims]``.
@@ -220,9 +211,7 @@ class NGCF(_FlatModel):
         which never switches modes here) and the dot product of the concatenated rows."""
         lib = self._require_hip()
         dev = self._flat.device
-        users_t, items_t = (x.to(dev, torch.int64).reshape(-1).contiguous() if torch.is_tensor(x) else
-                            torch.as_tensor(np.asarray(x), dtype=torch.int64).to(dev).reshape(-1).contiguous()
-                            for x in (users, items))
+        users_t, items_t = index_tensor(users, dev), index_tensor(items, dev)
         if users_t.numel() != items_t.numel():
             raise ValueError("users and items differ in length")
         stats = self._device_stats()
@@ -233,10 +222,7 @@ class NGCF(_FlatModel):
         scores = torch.empty(users_t.numel(), dtype=torch.float32, device=dev)
         _lib.check(lib.hiprec_ngcf_predict(ctypes.byref(plan), _lib.ptr(users_t), _lib.ptr(items_t),
                                            users_t.numel(), _lib.ptr(scores), _lib.ptr(stats), st))
-        s = read_stats(stats)
-        if s.status:
-            self._stats = None
-            raise_on_status(s.status)
+        self._check_status()
         return scores
 
 
@@ -257,8 +243,7 @@ class NGCFEngine(FlatModelEngine):
         lib = self._setup()
         m = self.model
         dev = m.flat.device
-        users, pos, neg = (torch.as_tensor(x, device=dev).to(torch.int64).reshape(-1).contiguous()
-                           for x in batch_data)
+        users, pos, neg = (index_tensor(x, dev) for x in batch_data)
         B = users.numel()
         if not (pos.numel() == B and neg.numel() == B):
             raise ValueError("batch tensors differ in length")
@@ -279,13 +264,7 @@ class NGCFEngine(FlatModelEngine):
     def train_an_epoch(self, train_loader, epoch_id):
         """ngcf.py:151-170: prints the last batch's loss and the (zero) regulariser sum, logs both."""
         assert hasattr(self, "model"), "Please specify the exact model !"
-        self.model.train()
-        lib = self._setup()
-        _lib.check(lib.hiprec_stats_begin_epoch(_lib.ptr(self._stats),
-                                                _lib.stream_ptr(self.model.flat.device)))
-        for batch_data in train_loader:
-            self._enqueue_step(batch_data)
-        st = self._sync_stats()
+        st = self._run_epoch(train_loader)
         regularizer = 0.0
         print(f"[Training Epoch {epoch_id}], Loss {st.loss}, Regularizer {regularizer}")
         self.writer.add_scalar("model/loss", st.loss_sum, epoch_id)

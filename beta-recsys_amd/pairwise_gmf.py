@@ -20,9 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .mf import _new_stats, raise_on_status, read_stats
-from .ncf import _FlatModel, _ParamView
-from .flat_engine import FlatModelEngine
+from .flat_engine import FlatModelEngine, _FlatModel, _ParamView, index_tensor
 from .torch_engine import HipOptimizer
 
 
@@ -58,7 +56,6 @@ class PairwiseGMF(_FlatModel):
         self.user_memory = _ParamView(v["user_memory.weight"])
         self.item_memory = _ParamView(v["item_memory.weight"])
         self.v = _ParamView(v["v.weight"])
-        self._stats = None
 
     def tables(self, flat=None):
         """hiprec_pgmf_tables over the weight buffer (or a same-shaped gradient buffer)."""
@@ -72,10 +69,8 @@ class PairwiseGMF(_FlatModel):
         leaves the D-wide dot to torch on the same device."""
         lib = self._require_hip()
         dev = self._flat.device
-        if self._stats is None or self._stats.device != dev:
-            self._stats = _new_stats(dev)
-        ids = [torch.as_tensor(x, device=dev).to(torch.int64).reshape(-1).contiguous()
-               for x in (input_users, input_items, input_items_negative)]
+        stats = self._device_stats()
+        ids = [index_tensor(x, dev) for x in (input_users, input_items, input_items_negative)]
         D = self.emb_dim
         rows = []
         for idx, (name, n_rows) in zip(ids, (("user_memory.weight", self.n_users),
@@ -83,13 +78,9 @@ class PairwiseGMF(_FlatModel):
                                              ("item_memory.weight", self.n_items))):
             out = torch.empty(idx.numel(), D, dtype=torch.float32, device=dev)
             _lib.check(lib.hiprec_gather_rows(_lib.ptr(self.views()[name]), n_rows, D, _lib.ptr(idx),
-                                              idx.numel(), _lib.ptr(out), _lib.ptr(self._stats),
-                                              _lib.stream_ptr(dev)))
+                                              idx.numel(), _lib.ptr(out), _lib.ptr(stats), _lib.stream_ptr(dev)))
             rows.append(out)
-        st = read_stats(self._stats)
-        if st.status:
-            self._stats = None
-            raise_on_status(st.status)
+        self._check_status()
         w = self.views()["v.weight"]
         return (torch.relu((rows[0] * rows[1]) @ w.t()), torch.relu((rows[0] * rows[2]) @ w.t()))
 
@@ -127,7 +118,7 @@ class PairwiseGMFEngine(FlatModelEngine):
         for x in batch_data:
             if not isinstance(x, torch.Tensor):
                 x = torch.from_numpy(np.array(x, dtype=np.int32))
-            out.append(x.to(dev).to(torch.int64).reshape(-1).contiguous())
+            out.append(index_tensor(x, dev))
         if not (out[0].numel() == out[1].numel() == out[2].numel()):
             raise ValueError("batch tensors differ in length")
         if out[0].numel() == 0:
@@ -172,7 +163,7 @@ class PairwiseGMFEngine(FlatModelEngine):
         lib = self._setup()
         m, opt = self.model, self.optimizer
         dev = m.flat.device
-        users, pos, neg = (x.to(dev).to(torch.int64).reshape(-1).contiguous() for x in (users, pos, neg))
+        users, pos, neg = (index_tensor(x, dev) for x in (users, pos, neg))
         if not (users.numel() == pos.numel() == neg.numel()):
             raise ValueError("epoch arrays differ in length")
         w, g = m.tables(), m.tables(self._g_flat)
@@ -200,8 +191,7 @@ class PairwiseGMFEngine(FlatModelEngine):
         blocks = [b if isinstance(b, torch.Tensor) else torch.from_numpy(np.array(b, dtype=np.int32)) for b in batches]
         if not blocks:
             raise ValueError("empty epoch")
-        if any(b.shape[0] != self.batch_size for b in blocks[:-1]) or blocks[-1].shape[0] > self.batch_size:
-            raise ValueError("every batch but the last must hold batch_size triples")
+        self._check_blocks([b.shape[0] for b in blocks], self.batch_size)
         epoch = torch.cat([b.to(dev).to(torch.int64).reshape(-1, 3) for b in blocks])
         self.enqueue_epoch(epoch[:, 0], epoch[:, 1], epoch[:, 2])
         st = self._sync_stats()

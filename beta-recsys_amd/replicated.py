@@ -20,6 +20,7 @@ import torch
 from . import _dist as dist
 
 from . import _lib
+from .flat_engine import index_tensor
 from .mf import MFEngine
 
 
@@ -389,8 +390,7 @@ class _ReplicatedNcfMixin:
         lib = self._setup()
         m, opt = self.model, self.optimizer
         dev = m.flat.device
-        users = torch.as_tensor(users, device=dev).to(torch.int64).reshape(-1).contiguous()
-        items = torch.as_tensor(items, device=dev).to(torch.int64).reshape(-1).contiguous()
+        users, items = index_tensor(users, dev), index_tensor(items, dev)
         ratings = torch.as_tensor(ratings, device=dev).to(torch.float32).reshape(-1).contiguous()
         B = users.numel()
         if not (items.numel() == B and ratings.numel() == B) or B == 0:

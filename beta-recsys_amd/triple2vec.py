@@ -25,9 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .mf import _new_stats, raise_on_status, read_stats
-from .ncf import _FlatModel, _ParamView
-from .flat_engine import FlatModelEngine
+from .flat_engine import FlatModelEngine, _FlatModel, _ParamView, index_tensor
 
 
 class Triple2vec(_FlatModel):
@@ -61,7 +59,6 @@ class Triple2vec(_FlatModel):
         self.item_emb2 = _ParamView(v["item_emb2.weight"])
         self.user_bias = _ParamView(v["user_bias.weight"])
         self.item_bias = _ParamView(v["item_bias.weight"])
-        self._stats = None
 
     # ---- the item_emb2 alias ------------------------------------------------------------------------
     @property
@@ -94,19 +91,6 @@ class Triple2vec(_FlatModel):
         return _lib.T2vTables(at("user_emb.weight"), e1, e2, at("user_bias.weight"), at("item_bias.weight"),
                               self.n_users, self.n_items, self.emb_dim, 0)
 
-    def _device_stats(self):
-        dev = self._flat.device
-        if self._stats is None or self._stats.device != dev:
-            self._stats = _new_stats(dev)
-        return self._stats
-
-    def _check_status(self):
-        s = read_stats(self._stats)
-        if s.status:
-            self._stats = None
-            raise_on_status(s.status)
-        return s
-
     # ---- reference API -------------------------------------------------------------------------------
     def forward(self, batch_data):
         """triple2vec.py:36-92: the batch loss as a 0-dim tensor (no autograd graph: training goes
@@ -125,9 +109,7 @@ class Triple2vec(_FlatModel):
         """triple2vec.py:94-104."""
         lib = self._require_hip()
         dev = self._flat.device
-        users_t, items_t = (x.to(dev, torch.int64).reshape(-1).contiguous() if torch.is_tensor(x) else
-                            torch.as_tensor(np.asarray(x), dtype=torch.int64).to(dev).reshape(-1).contiguous()
-                            for x in (users, items))
+        users_t, items_t = index_tensor(users, dev), index_tensor(items, dev)
         if users_t.numel() != items_t.numel():
             raise ValueError("users and items differ in length")
         stats = self._device_stats()
@@ -144,7 +126,7 @@ def _batch_tensors(model, batch_data):
     if len(batch_data) != 6:
         raise ValueError("Triple2vec batches are (pos_u, pos_i_1, pos_i_2, neg_u, neg_i_1, neg_i_2)")
     dev = model.flat.device
-    t = [torch.as_tensor(x, device=dev).to(torch.int64).contiguous() for x in batch_data]
+    t = [index_tensor(x, dev) for x in batch_data]          # the negatives' [B, n_neg] flattened, row-major
     B = t[0].numel()
     if B == 0:
         raise ValueError("empty batch")
@@ -239,7 +221,7 @@ class Triple2vecEngine(FlatModelEngine):
         m, opt = self.model, self.optimizer
         m._alias()
         dev = m.flat.device
-        t = [x.to(dev).to(torch.int64).contiguous() for x in (pos_u, pos_i1, pos_i2, neg_u, neg_i1, neg_i2)]
+        t = [index_tensor(x, dev) for x in (pos_u, pos_i1, pos_i2, neg_u, neg_i1, neg_i2)]
         N = t[0].numel()
         if N == 0:
             raise ValueError("empty epoch")
@@ -270,9 +252,7 @@ class Triple2vecEngine(FlatModelEngine):
                 negs.append(self._negatives(sample.shape[0], epoch_id, batch_id))
         if not blocks:
             raise ValueError("empty epoch")
-        B = self.model.batch_size
-        if any(b.shape[0] != B for b in blocks[:-1]) or blocks[-1].shape[0] > B:
-            raise ValueError("every batch but the last must hold batch_size triples")
+        self._check_blocks([b.shape[0] for b in blocks], self.model.batch_size)
         epoch = torch.cat(blocks)
         if self.negative_sampler == "host":
             neg = [torch.cat([n[k] for n in negs]) for k in range(3)]

@@ -30,9 +30,7 @@ import torch
 
 from . import _lib
 from .data import DeviceTensorBatcher
-from .flat_engine import FlatModelEngine
-from .mf import _new_stats, raise_on_status, read_stats
-from .ncf import _FlatModel, _ParamView
+from .flat_engine import FlatModelEngine, _FlatModel, _ParamView, index_tensor
 
 
 def get_ii_constraint_mat(train_mat, num_neighbors, ii_diagonal_zero=False):
@@ -116,7 +114,6 @@ class UltraGCN(_FlatModel):
         self.ii_neighbor_mat, self.ii_constraint_mat = nbr.contiguous(), sim.contiguous()
         self.initial_weights()
         self._consts = None
-        self._stats = None
 
     def initial_weights(self):
         """ultragcn.py:68-70."""
@@ -148,30 +145,16 @@ class UltraGCN(_FlatModel):
     def batch_tensors(self, users, pos_items, neg_items):
         """``(users[B], pos[B], neg[B, N])`` as contiguous int64 tensors on the weights' device, and ``N``."""
         dev = self._flat.device
-        t = [x.to(dev, torch.int64) if torch.is_tensor(x) else torch.as_tensor(np.asarray(x), dtype=torch.int64).to(dev)
-             for x in (users, pos_items, neg_items)]
-        users_t, pos_t = t[0].reshape(-1).contiguous(), t[1].reshape(-1).contiguous()
+        users_t, pos_t = index_tensor(users, dev), index_tensor(pos_items, dev)
+        neg = neg_items if torch.is_tensor(neg_items) else np.asarray(neg_items)
         B = users_t.numel()
         if B == 0:
             raise ValueError("empty batch")
         if pos_t.numel() != B:
             raise ValueError("users and pos_items differ in length")
-        if t[2].dim() != 2 or t[2].shape[0] != B or t[2].shape[1] < 1:
+        if neg.ndim != 2 or neg.shape[0] != B or neg.shape[1] < 1:
             raise ValueError("neg_items must be [batch, n_neg] with n_neg >= 1")
-        return users_t, pos_t, t[2].contiguous(), int(t[2].shape[1])
-
-    def _device_stats(self):
-        dev = self._flat.device
-        if self._stats is None or self._stats.device != dev:
-            self._stats = _new_stats(dev)
-        return self._stats
-
-    def _check_status(self):
-        s = read_stats(self._stats)
-        if s.status:
-            self._stats = None
-            raise_on_status(s.status)
-        return s
+        return users_t, pos_t, index_tensor(neg, dev).view(neg.shape), int(neg.shape[1])
 
     # ---- reference API -----------------------------------------------------------------------------------
     def get_omegas(self, users, pos_items, neg_items):
@@ -203,9 +186,7 @@ class UltraGCN(_FlatModel):
         """ultragcn.py:167-179."""
         lib = self._require_hip()
         dev = self._flat.device
-        users_t, items_t = (x.to(dev, torch.int64).reshape(-1).contiguous() if torch.is_tensor(x) else
-                            torch.as_tensor(np.asarray(x), dtype=torch.int64).to(dev).reshape(-1).contiguous()
-                            for x in (users, items))
+        users_t, items_t = index_tensor(users, dev), index_tensor(items, dev)
         if users_t.numel() != items_t.numel():
             raise ValueError("users and items differ in length")
         stats = self._device_stats()
@@ -307,8 +288,7 @@ class UltraGCNEngine(FlatModelEngine):
             if not blocks:
                 raise ValueError("empty epoch")
             batch_size = blocks[0][0].numel()
-            if any(b[0].numel() != batch_size for b in blocks[:-1]) or blocks[-1][0].numel() > batch_size:
-                raise ValueError("every batch but the last must hold the same number of samples")
+            self._check_blocks([b[0].numel() for b in blocks], batch_size, "the same number of samples")
             if len({b[2].shape[1] for b in blocks}) != 1:
                 raise ValueError("batches differ in the number of negatives")
             cols = [torch.cat([b[k] for b in blocks]) for k in range(3)]

@@ -161,6 +161,15 @@ def test_ncf_errors(hip_device):
     assert np.isfinite(eng.train_single_batch(*ok))
     one = eng.train_single_batch(torch.tensor([1]), torch.tensor([2]), torch.tensor([1.0]))
     assert np.isfinite(one)  # unlike MF, a batch of one is legal for the NCF family
+    # backward_only after a refused batch: the valid sample's partial gradient must not leak into the next call
+    loss0, g0 = eng.backward_only(*ok)
+    with pytest.raises(IndexError):
+        eng.backward_only(torch.tensor([1, 10]), torch.tensor([3, 4]), torch.tensor([1.0, 0.0]))
+    loss1, g1 = eng.backward_only(*ok)
+    assert np.array_equal(np.float64(loss1), np.float64(loss0))
+    assert sorted(g1) == sorted(g0)
+    for k in g0:
+        assert np.array_equal(g1[k].cpu().numpy(), g0[k].cpu().numpy()), k
 
 
 @pytest.mark.parametrize("E", [32, 64])
