@@ -17,3 +17,5 @@ from .triple2vec import Triple2vec, Triple2vecEngine  # noqa: F401
 from .ultragcn import UltraGCN, UltraGCNEngine, get_ii_constraint_mat  # noqa: F401
 from . import eval  # noqa: F401,A004  (evaluate / predict / rank_metrics)
 from . import data  # noqa: F401  (device-side loaders / negative sampling)
+from .recommend import recommend  # noqa: F401  (top-K over the whole catalogue, csrc/topk.hip)
+from .eval import evaluate_full  # noqa: F401

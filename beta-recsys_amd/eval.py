@@ -119,6 +119,97 @@ def evaluate(data_df, predictions, metrics, k_li, device=None):
     return {f"{m}@{k}": result[f"{m}@{k}"] for k in k_li for m in metrics}
 
 
+def topk_metrics(items, truth_ptr, truth_sorted, k_list):
+    """(n_common_users, table[len(k_list), 4] float64 numpy; columns precision, recall, ndcg, map) of ranked lists
+    ``items[n, k]`` (device int64, -1 = padding) against a truth CSR with one row per list (``hiprec_topk_metrics``)."""
+    k_list = [int(k) for k in k_list]
+    if not 1 <= len(k_list) <= MAX_K:
+        raise ValueError(f"between 1 and {MAX_K} cut-offs per call, got {len(k_list)}")
+    n, k = int(items.shape[0]), int(items.shape[1])
+    if min(k_list) < 1 or max(k_list) > k:
+        raise ValueError(f"cut-offs must be in 1..{k} (the lists' length), got {k_list}")
+    dev = _resolve_device(items.device)
+    lib = _lib.load()
+    items = items.to(torch.int64).contiguous()
+    truth_ptr = truth_ptr.to(dev, torch.int64).contiguous()
+    truth_sorted = truth_sorted.to(dev, torch.int64).contiguous()
+    if truth_ptr.numel() != n + 1:
+        raise ValueError(f"truth_ptr must hold {n + 1} entries, got {truth_ptr.numel()}")
+    n_k = len(k_list)
+    ws_bytes = lib.hiprec_rank_metrics_workspace_bytes(n, n_k)
+    workspace = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
+    out = torch.empty(1 + 4 * n_k, dtype=torch.float64, device=dev)
+    ks = (ctypes.c_int32 * n_k)(*k_list)
+    _lib.check(lib.hiprec_topk_metrics(_lib.ptr(items), n, k, _lib.ptr(truth_ptr), _lib.ptr(truth_sorted), ks, n_k,
+                                       _lib.ptr(workspace), ws_bytes, _lib.ptr(out), _lib.stream_ptr(dev)))
+    host = out.cpu().numpy()
+    return int(host[0]), host[1:].reshape(n_k, 4).copy()
+
+
+def evaluate_full(model, test_df, train_df=None, metrics=RANK_METRICS, k_li=(5, 10, 20), item_splits=0):
+    """Full-catalogue ranking evaluation, the protocol of the LightGCN / UltraGCN papers: for every user of
+    ``test_df`` the candidates are ALL items not in the user's ``train_df`` rows, the truth is the user's ``test_df``
+    rows with rating >= 1 (every row when the frame has no rating column; an item that is also in the user's training
+    rows is no candidate and does not count), and the metrics are those of :func:`evaluate`, in its
+    ``{f"{metric}@{k}": value}`` form and key order.  Computed as ``recommend`` at ``max(k_li)`` followed by
+    ``hiprec_topk_metrics``: no candidate frame and no score matrix is built.  ``model``: a model with
+    ``ranking_factors()`` or its engine."""
+    from .recommend import ranking_factors, topk_factors    # (recommend imports data, which imports this module)
+
+    unknown = [m for m in metrics if m not in RANK_METRICS]
+    if unknown:
+        raise KeyError(f"metrics {unknown} are not ranking metrics; supported: {RANK_METRICS}")
+    if type(k_li) not in (list, tuple):
+        k_li = [k_li]
+    k_li = [int(k) for k in k_li]
+    engine = model if hasattr(model, "model") and not hasattr(model, "ranking_factors") else None
+    if engine is not None:
+        if hasattr(engine, "flush_lazy"):
+            engine.flush_lazy()
+        model = engine.model
+    U, I, alpha, bias = ranking_factors(model)
+    dev = U.device
+    n_users, n_items = int(U.shape[0]), int(I.shape[0])
+    as_ids = lambda col: torch.as_tensor(np.asarray(col)).to(dev, torch.int64).reshape(-1)  # noqa: E731
+    t_users, t_items = as_ids(_column(test_df, DEFAULT_USER_COL)), as_ids(_column(test_df, DEFAULT_ITEM_COL))
+    try:
+        ratings = torch.as_tensor(np.asarray(_column(test_df, DEFAULT_RATING_COL))).to(dev).reshape(-1)
+        keep = ratings >= 1
+    except KeyError:
+        keep = torch.ones_like(t_users, dtype=torch.bool)
+    from .data import build_positive_csr
+
+    seen = None
+    if train_df is not None:
+        s_users, s_items = as_ids(_column(train_df, DEFAULT_USER_COL)), as_ids(_column(train_df, DEFAULT_ITEM_COL))
+        seen = build_positive_csr(s_users, s_items, n_users, n_items)
+        if s_users.numel():
+            seen_keys = torch.unique(s_users * n_items + s_items)
+            keep = keep & ~torch.isin(t_users * n_items + t_items, seen_keys)
+    query = torch.unique(t_users)                                   # ascending
+    truth_ptr_all, truth_sorted = build_positive_csr(t_users[keep], t_items[keep], n_users, n_items)
+    if query.numel() and (int(query.min()) < 0 or int(query.max()) >= n_users):
+        raise IndexError("test frame holds a user id outside [0, n_users)")
+    k_max = max(k_li)
+    items, _ = topk_factors(U, I, alpha, bias, query, k_max, seen, item_splits)
+    # the truth rows of the query users, in query order: a CSR over the same pos array needs its rows contiguous, so
+    # gather the lengths and rebuild the pointer; the rows themselves are copied in order
+    lens = truth_ptr_all[query + 1] - truth_ptr_all[query]
+    truth_ptr = torch.zeros(query.numel() + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(lens, 0, out=truth_ptr[1:])
+    owner = torch.repeat_interleave(torch.arange(query.numel(), device=dev), lens)
+    offs = torch.arange(int(lens.sum()), device=dev) - truth_ptr[owner] + truth_ptr_all[query][owner]
+    truth_q = truth_sorted[offs]
+    result = {}
+    for lo in range(0, len(k_li), MAX_K):
+        chunk = k_li[lo:lo + MAX_K]
+        _, table = topk_metrics(items, truth_ptr, truth_q, chunk)
+        for j, k in enumerate(chunk):
+            for metric in metrics:
+                result[f"{metric}@{k}"] = float(table[j, RANK_METRICS.index(metric)])
+    return {f"{m}@{k}": result[f"{m}@{k}"] for k in k_li for m in metrics}
+
+
 def predict_device(data_df, model, batch_size=None):
     """Scores of every row as ONE device tensor (no host copy), optionally in batches."""
     user_ids = np.asarray(_column(data_df, DEFAULT_USER_COL))

@@ -535,6 +535,19 @@ class LightGCN(_FlatModel):
         out = self._ws["acc"] / float(self.n_layers + 1)
         return torch.split(out, [self.n_users, self.n_items])
 
+    def ranking_factors(self):
+        """``(U, I, alpha, None)`` for full-catalogue ranking (``recommend.recommend``): eval-mode propagation as in
+        ``predict``, then the two halves of the accumulated layer sum -- the layer mean is that sum over ``L + 1`` on
+        both sides of the dot product, hence ``alpha = 1 / (L + 1)^2``.  The sigmoid of ``predict`` is monotonic and
+        left out."""
+        self.eval()
+        self._staged_for = None              # the propagation below overwrites what an optimizer launch may have staged
+        lib = self._require_hip()
+        plan = self.plan()
+        _lib.check(lib.hiprec_lightgcn_propagate(ctypes.byref(plan), None, 1.0, _lib.stream_ptr(self._flat.device)))
+        acc = self._ws["acc"]
+        return acc[: self.n_users], acc[self.n_users:], 1.0 / float(self.n_layers + 1) ** 2, None
+
     def predict(self, users, items):
         """lightgcn.py:80-101: eval mode, full propagation, sigmoid of the dot product."""
         self.eval()

@@ -284,6 +284,14 @@ class MF(nn.Module):
         )
         return scores
 
+    def ranking_factors(self):
+        """``(U, I, alpha, item_bias)`` for full-catalogue ranking (``recommend.recommend``): the two tables and the
+        item bias.  ``predict`` is ``sigmoid(dot + user_bias + item_bias + global_bias)``; the user bias, the global bias
+        and the sigmoid (monotonic) do not change the order of one user's items and are left out, so the scores that
+        come back are the logits minus ``user_bias[u] + global_bias``."""
+        self._require_hip()
+        return self.user_emb.weight.data, self.item_emb.weight.data, 1.0, self.item_bias.weight.data.reshape(-1)
+
     def predict(self, users, items):
         """mf.py:57-70: numpy / list ids in, score tensor on the device out."""
         dev = self._flat.device

@@ -188,6 +188,12 @@ class _NcfBase(_FlatModel):
         self._check_status()
         return scores
 
+    def ranking_factors(self):
+        """The NeuMF family has no ranking factors: its score runs the pair through an MLP tower / a learned output
+        layer and is not bilinear in a user row and an item row, so ``recommend`` cannot serve it."""
+        raise NotImplementedError(f"{type(self).__name__} is not bilinear (its score passes through an MLP / output "
+                                  "layer): full-catalogue ranking needs score = dot(user row, item row)")
+
     def init_weight(self):
         """models/ncf.py:80-82 (a no-op there); GMF / MLP override."""
 

@@ -206,6 +206,17 @@ class NGCF(_FlatModel):
         e0 = self._flat[: N * d0].view(N, d0)      # hop 0's slice of the concatenation is the tables themselves
         return torch.split(torch.cat([e0, self._ws["all"][:, d0:]], dim=1), [self.n_users, self.n_items], dim=0)
 
+    def ranking_factors(self):
+        """``(U, I, 1.0, None)`` for full-catalogue ranking (``recommend.recommend``): an eval-mode forward (no message
+        dropout, whatever mode the model is in; the mode is restored) and the concatenated layer outputs."""
+        was_training = self.training
+        self.eval()
+        try:
+            users, items = self.forward()
+        finally:
+            self.train(was_training)
+        return users, items, 1.0, None
+
     def predict(self, users, items):
         """ngcf.py:82-100: a full forward (dropout follows ``self.training`` exactly like the reference,
         which never switches modes here) and the dot product of the concatenated rows."""

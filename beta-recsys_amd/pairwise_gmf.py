@@ -87,6 +87,10 @@ class PairwiseGMF(_FlatModel):
     def predict(self):
         """pairwise_gmf.py:64-66: a stub in the reference as well."""
 
+    def ranking_factors(self):
+        """No ranking factors: the reference defines no prediction for this model (its ``predict`` is a stub)."""
+        raise NotImplementedError("PairwiseGMF has no prediction to rank by: predict is a stub in the reference as well")
+
 
 class PairwiseGMFEngine(FlatModelEngine):
     """models/pairwise_gmf.py:69-158."""

@@ -159,6 +159,12 @@ class ModelEngine(object):
         """torch_engine.py:58-68: likewise overridden by every engine."""
         raise NotImplementedError("engines implement train_an_epoch")
 
+    def recommend(self, users, k, seen=None, item_splits=0):
+        """The ``k`` best unseen items of the whole catalogue per query user: ``recommend.recommend`` on this engine."""
+        from .recommend import recommend
+
+        return recommend(self, users, k, seen, item_splits)
+
     OPT_STATE_SUFFIX = ".opt"          # the optional second file of a checkpoint: optimizer clock + moments
     OPT_STATE_FORMAT = "hiprec-optimizer-state-1"
 

@@ -105,6 +105,10 @@ class Triple2vec(_FlatModel):
         _lib.check(lib.hiprec_finalize_stats(_lib.ptr(stats), _lib.ptr(scratch), None, None, _lib.stream_ptr(dev)))
         return torch.tensor(self._check_status().loss, device=dev)
 
+    def ranking_factors(self):
+        """Not offered yet: Triple2vec's score needs an item table derived from its two item embeddings."""
+        raise NotImplementedError("Triple2vec needs a derived item table for full-catalogue ranking; not implemented yet")
+
     def predict(self, users, items):
         """triple2vec.py:94-104."""
         lib = self._require_hip()

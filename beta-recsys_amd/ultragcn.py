@@ -182,6 +182,12 @@ class UltraGCN(_FlatModel):
         _lib.check(lib.hiprec_finalize_stats(_lib.ptr(stats), _lib.ptr(scratch), None, None, _lib.stream_ptr(dev)))
         return torch.tensor(self._check_status().loss, device=dev)
 
+    def ranking_factors(self):
+        """``(U, I, 1.0, None)`` for full-catalogue ranking (``recommend.recommend``): the two tables; ``predict`` is
+        their dot product."""
+        self._require_hip()
+        return self.user_embeds.weight.data, self.item_embeds.weight.data, 1.0, None
+
     def predict(self, users, items):
         """ultragcn.py:167-179."""
         lib = self._require_hip()

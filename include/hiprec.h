@@ -1052,6 +1052,42 @@ int hiprec_rank_metrics(const int64_t* seg_ptr, int64_t n_segments, const float*
                         const float* ratings, const int32_t* k_list_host, int32_t n_k,
                         double* workspace, size_t workspace_bytes, double* out, void* stream);
 
+/* ================= Top-K recommendation over the whole catalogue (csrc/topk.hip) ====
+ * For every query user q (query_users[n_query], device int64) the k best items of
+ *   score(u, i) = alpha * dot(U[u, 0:dim], I[i, 0:dim]) + (item_bias ? item_bias[i] : 0)        (fp32)
+ * among the items NOT in the user's row of the seen-item CSR (user_ptr[n_users+1], pos_sorted: device int64, ascending
+ * and unique per user -- what data.build_positive_csr returns; both NULL = nothing is masked).  U [n_users, dim] and
+ * I [n_items, dim] are row-major fp32 with leading dimensions ldu / ldi (floats; >= dim).
+ * Order: score descending, ties to the lower item id; -0.0 ties with +0.0 (and comes back as +0.0).  out_items
+ * [n_query, k] (int64) and out_scores [n_query, k] (fp32); a user with fewer than k unseen items gets -1 / -inf in the
+ * tail.  A query user outside [0, n_users) sets HIPREC_STATUS_USER_OOB and its row is all -1 / -inf.  NaN factors:
+ * unspecified.
+ * One launch scores 64 query users per block against the item tiles of one of `item_splits` contiguous item ranges
+ * (0 = chosen by the library from n_query and n_items) and keeps a running top-k per user in LDS; a second launch merges
+ * the per-range lists (workspace) and writes the outputs.  The bits of score(u, i) depend on the two rows and dim only
+ * (a fixed-order fp32 fma chain on the 16x16x4 fp32 MFMA), so the result does not depend on item_splits.
+ * Limits: 1 <= k <= HIPREC_TOPK_MAX_K, 1 <= dim <= HIPREC_TOPK_MAX_DIM, 1 <= n_items < 2^32 - 1.
+ * workspace: hiprec_topk_workspace_bytes(n_query, n_items, k, item_splits) bytes of device memory (0 for bad sizes). */
+#define HIPREC_TOPK_MAX_K 128
+#define HIPREC_TOPK_MAX_DIM 512
+#define HIPREC_TOPK_MAX_SPLITS 64
+size_t hiprec_topk_workspace_bytes(int64_t n_query, int64_t n_items, int32_t k, int32_t item_splits);
+int hiprec_topk_recommend(const float* user_factors, int64_t ldu, int64_t n_users, const float* item_factors,
+                          int64_t ldi, int64_t n_items, int32_t dim, float alpha, const float* item_bias,
+                          const int64_t* query_users, int64_t n_query, const int64_t* user_ptr,
+                          const int64_t* pos_sorted, int32_t k, int32_t item_splits, void* workspace,
+                          size_t workspace_bytes, int64_t* out_items, float* out_scores, hiprec_stats* stats,
+                          void* stream);
+
+/* Ranking metrics of recommendation lists against a ground-truth CSR: row q of items [n_query, k] (device int64, -1 =
+ * padding) is user q's ranked list, truth_ptr[n_query+1] / truth_sorted (device int64, ascending and unique per row) its
+ * relevant items.  A hit is membership in the truth row; a user with no truth item contributes nothing.  Definitions,
+ * k_list_host (each cut-off <= k) and the fp64 output block are those of hiprec_rank_metrics; workspace:
+ * hiprec_rank_metrics_workspace_bytes(n_query, n_k) bytes. */
+int hiprec_topk_metrics(const int64_t* items, int64_t n_query, int32_t k, const int64_t* truth_ptr,
+                        const int64_t* truth_sorted, const int32_t* k_list_host, int32_t n_k, double* workspace,
+                        size_t workspace_bytes, double* out, void* stream);
+
 /* ================= PairwiseGMF, the CMN pre-training model (sibling models) ====
  * models/pairwise_gmf.py:28-46 parameters: user_memory [n_users, dim], item_memory [n_items, dim],
  * v = nn.Linear(dim, 1, bias=False).weight [1, dim].  The host keeps them in ONE flat buffer in that
