@@ -15,6 +15,9 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("HIPREC_LIB", "libhiprec.so"))
 
 OPT_SGD, OPT_ADAM, OPT_RMSPROP = 0, 1, 2
 OPT_KINDS = {"sgd": OPT_SGD, "adam": OPT_ADAM, "rmsprop": OPT_RMSPROP}
+# torch.optim.RMSprop(momentum > 0), cmn.py's own optimizer: no config name of the reference selects it, so it is
+# not in OPT_KINDS (HipOptimizer("rmsprop", lr, momentum=...) does)
+OPT_RMSPROP_MOMENTUM = 3
 
 STATUS_USER_OOB, STATUS_ITEM_OOB, STATUS_ROW_OOB, STATUS_ROUTE_OVERFLOW = 1, 2, 4, 8
 STATUS_NEG_EXHAUSTED = 16
@@ -111,6 +114,14 @@ class PgmfTables(Structure):
 
     _fields_ = [("user_memory", c_void_p), ("item_memory", c_void_p), ("v", c_void_p),
                 ("n_users", c_int64), ("n_items", c_int64), ("dim", c_int32), ("_pad", c_int32)]
+
+
+class CmnTables(Structure):
+    """hiprec_cmn_tables (include/hiprec.h)."""
+
+    _fields_ = [(n, c_void_p) for n in ("user_memory", "item_memory", "user_output", "hop_w", "hop_b", "dense_w",
+                                        "dense_b", "out_w")] + \
+               [("n_users", c_int64), ("n_items", c_int64), ("dim", c_int32), ("_pad", c_int32)]
 
 
 class UltraGcnTables(Structure):
@@ -320,6 +331,24 @@ SIGNATURES = {
     "hiprec_pgmf_epoch": (
         c_int,
         [POINTER(PgmfTables), POINTER(PgmfTables), _P, _P, _P, c_int64, c_int64, c_float, c_float, c_int,
+         c_double, c_double, c_double, c_double, _P, _P, _P, _P, c_int64, _P, _P, c_size_t, _P, c_size_t,
+         _P, c_size_t, _P],
+    ),
+    "hiprec_cmn_tables_bytes": (c_size_t, []),
+    "hiprec_cmn_workspace_bytes": (c_size_t, [c_int32, c_int64]),
+    "hiprec_cmn_grad_padded": (
+        c_int,
+        [POINTER(CmnTables), POINTER(CmnTables), _P, _P, _P, _P, _P, c_int64, _P, _P, c_int64, c_int64, c_float,
+         c_float, _P, _P, _P, _P, c_size_t, _P, c_size_t, _P],
+    ),
+    "hiprec_cmn_grad_csr": (
+        c_int,
+        [POINTER(CmnTables), POINTER(CmnTables), _P, _P, _P, _P, _P, c_int64, c_float, c_float, _P, _P, _P, _P,
+         c_size_t, _P, c_size_t, _P],
+    ),
+    "hiprec_cmn_epoch": (
+        c_int,
+        [POINTER(CmnTables), POINTER(CmnTables), _P, _P, _P, _P, _P, c_int64, c_int64, c_float, c_float, c_int,
          c_double, c_double, c_double, c_double, _P, _P, _P, _P, c_int64, _P, _P, c_size_t, _P, c_size_t,
          _P, c_size_t, _P],
     ),
@@ -541,6 +570,8 @@ def load():
         raise RuntimeError("hiprec_lazy_state layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_shard_bufs_bytes() != ctypes.sizeof(ShardBufs):
         raise RuntimeError("hiprec_shard_bufs layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_cmn_tables_bytes() != ctypes.sizeof(CmnTables):
+        raise RuntimeError("hiprec_cmn_tables layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_ncf_plan_bytes() != ctypes.sizeof(NcfPlan):
         raise RuntimeError("hiprec_ncf_plan layout mismatch between _lib.py and libhiprec.so")
     _lib = _DeviceGuardedLib(lib)

@@ -284,7 +284,11 @@ __device__ __forceinline__ void advance_step(hiprec_stats* stats) {
 struct OptScalars {
   double lr_d;
   float lr, beta2, omb1, omb2, eps;
+  float mu = 0.f;   // HIPREC_OPT_RMSPROP_MOMENTUM only: (float)momentum
 };
+
+// kinds that keep a first state buffer m (Adam's exp_avg, RMSprop-with-momentum's momentum buffer)
+constexpr bool opt_has_m(int kind) { return kind == HIPREC_OPT_ADAM || kind == HIPREC_OPT_RMSPROP_MOMENTUM; }
 
 // Division and square root of the Adam / RMSprop denominators.  The default uses the hardware
 // v_rcp_f32 / v_sqrt_f32 (1 ulp each): the update then differs from ATen's correctly rounded
@@ -321,6 +325,16 @@ __device__ __forceinline__ void opt_update(float& w, float& g, float& m, float& 
       const float denom = __builtin_fmaf(__builtin_amdgcn_sqrtf(v), r_bc2, s.eps);
       w = __builtin_fmaf(num, __builtin_amdgcn_rcpf(denom), w);
 #endif
+    } else if constexpr (KIND == HIPREC_OPT_RMSPROP_MOMENTUM) {
+      // avg = square_avg.sqrt().add_(eps); buf.mul_(momentum).addcdiv_(grad, avg); param.add_(buf, alpha=-lr)
+#ifdef HIPREC_IEEE_DIV
+      const float avg = sqrtf(v) + s.eps;
+      m = m * s.mu + g / avg;
+#else
+      const float avg = __builtin_amdgcn_sqrtf(v) + s.eps;
+      m = __builtin_fmaf(g, __builtin_amdgcn_rcpf(avg), m * s.mu);
+#endif
+      w = __builtin_fmaf(-s.lr, m, w);
     } else {
       const float num = -s.lr * g;  // param.addcdiv_(grad, avg, value=-lr)
 #ifdef HIPREC_IEEE_DIV

@@ -1,6 +1,7 @@
 // Dense optimizer sweeps: torch.optim.{SGD,Adam,RMSprop}.step() as configured by
 // beta_rec/models/torch_engine.py:23-39 (only `lr` given => Adam betas (0.9, 0.999), eps 1e-8,
-// RMSprop alpha 0.99 eps 1e-8, no momentum, no weight decay, no amsgrad).
+// RMSprop alpha 0.99 eps 1e-8, no momentum, no weight decay, no amsgrad), and RMSprop WITH momentum
+// (HIPREC_OPT_RMSPROP_MOMENTUM), the optimizer models/cmn.py:147-149 builds for itself.
 //
 // nn.Embedding is non-sparse in the reference, so autograd produces DENSE gradients and Adam /
 // RMSprop move every element whose moments are non-zero on every step, touched by the batch or
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(kBlock) void opt_dense_kernel(float* __restrict__ w
     if (i == skip4) continue;
     float4 wv = w4[i], gv = g4[i];
     float4 mv = make_float4(0, 0, 0, 0), vv = make_float4(0, 0, 0, 0);
-    if constexpr (KIND == HIPREC_OPT_ADAM) mv = m4[i];
+    if constexpr (opt_has_m(KIND)) mv = m4[i];
     if constexpr (KIND != HIPREC_OPT_SGD) vv = v4[i];
     if (scale) {
       gv.x *= coef;
@@ -82,19 +83,19 @@ __global__ __launch_bounds__(kBlock) void opt_dense_kernel(float* __restrict__ w
     opt_update<KIND>(wv.w, gv.w, mv.w, vv.w, s, step_size, bc2_sqrt);
     w4[i] = wv;
     g4[i] = gv;
-    if constexpr (KIND == HIPREC_OPT_ADAM) m4[i] = mv;
+    if constexpr (opt_has_m(KIND)) m4[i] = mv;
     if constexpr (KIND != HIPREC_OPT_SGD) v4[i] = vv;
   }
   auto scalar_update = [&](int64_t i, float extra_g) {
     float wv = w[i], gv = g[i], mv = 0.f, vv = 0.f;
     if (scale) gv *= coef;
     gv += extra_g;
-    if constexpr (KIND == HIPREC_OPT_ADAM) mv = m[i];
+    if constexpr (opt_has_m(KIND)) mv = m[i];
     if constexpr (KIND != HIPREC_OPT_SGD) vv = v[i];
     opt_update<KIND>(wv, gv, mv, vv, s, step_size, bc2_sqrt);
     w[i] = wv;
     g[i] = gv;
-    if constexpr (KIND == HIPREC_OPT_ADAM) m[i] = mv;
+    if constexpr (opt_has_m(KIND)) m[i] = mv;
     if constexpr (KIND != HIPREC_OPT_SGD) v[i] = vv;
   };
   for (int64_t i = (n4 << 2) + tid; i < n; i += stride) {  // scalar tail (< 4 elements)
@@ -133,7 +134,8 @@ int opt_dense_step_impl(int kind, float* w, float* g, float* m, float* v, int64_
                      static_cast<float>(beta2),
                      static_cast<float>(1.0 - beta1),
                      static_cast<float>(1.0 - beta2),
-                     static_cast<float>(eps)};
+                     static_cast<float>(eps),
+                     static_cast<float>(beta1)};
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int grid = grid_for_threads((n + 3) / 4);
   const auto* sc = static_cast<const Scratch*>(scratch);
@@ -156,6 +158,10 @@ int opt_dense_step_impl(int kind, float* w, float* g, float* m, float* v, int64_
     case HIPREC_OPT_RMSPROP:
       HIPREC_REQUIRE(v, "rmsprop needs a square_avg buffer");
       HIPREC_OPT_LAUNCH(HIPREC_OPT_RMSPROP);
+      break;
+    case HIPREC_OPT_RMSPROP_MOMENTUM:
+      HIPREC_REQUIRE(m && v, "rmsprop with momentum needs a momentum buffer and a square_avg buffer");
+      HIPREC_OPT_LAUNCH(HIPREC_OPT_RMSPROP_MOMENTUM);
       break;
     default:
       set_error("unknown optimizer kind %d", kind);

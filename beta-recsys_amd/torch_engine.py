@@ -43,6 +43,7 @@ class HipOptimizer:
     Only ``lr`` is configurable in the reference; everything else is the torch default:
     Adam betas (0.9, 0.999) eps 1e-8; RMSprop alpha 0.99 eps 1e-8; SGD momentum 0.
     State lives in flat fp32 buffers laid out like the model's flat parameter buffer.
+    ``momentum`` (RMSprop only) is the one exception: models/cmn.py:147-149 builds ``RMSprop(lr, momentum=...)``.
     """
 
     DEFAULTS = {
@@ -51,7 +52,7 @@ class HipOptimizer:
         "rmsprop": dict(beta1=0.0, beta2=0.99, eps=1e-8),  # beta2 plays alpha
     }
 
-    def __init__(self, name, lr):
+    def __init__(self, name, lr, momentum=0.0):
         if name not in _lib.OPT_KINDS:
             raise ValueError(
                 f"Unsupported optimizer {name!r}: the engine supports 'sgd', 'adam', 'rmsprop' "
@@ -62,13 +63,21 @@ class HipOptimizer:
         self.lr = float(lr)
         d = self.DEFAULTS[name]
         self.beta1, self.beta2, self.eps = d["beta1"], d["beta2"], d["eps"]
+        self.momentum = float(momentum)
+        if self.momentum:
+            # torch.optim.RMSprop(momentum=mu), what models/cmn.py:147-149 builds: the momentum buffer lives in
+            # exp_avg, mu travels as beta1
+            if name != "rmsprop" or self.momentum < 0:
+                raise ValueError("momentum is RMSprop's (models/cmn.py:147-149) and must be >= 0")
+            self.kind = _lib.OPT_RMSPROP_MOMENTUM
+            self.beta1 = self.momentum
         self.exp_avg = None      # Adam m           (flat, zeros)
         self.exp_avg_sq = None   # Adam v / RMSprop square_avg
         self.defaults = {"lr": self.lr}
         if name == "adam":
             self.defaults.update(betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False)
         elif name == "rmsprop":
-            self.defaults.update(alpha=0.99, eps=1e-8, weight_decay=0, momentum=0, centered=False)
+            self.defaults.update(alpha=0.99, eps=1e-8, weight_decay=0, momentum=self.momentum or 0, centered=False)
         else:
             self.defaults.update(momentum=0, dampening=0, weight_decay=0, nesterov=False)
         self.param_groups = [dict(self.defaults)]
@@ -80,6 +89,8 @@ class HipOptimizer:
             self.exp_avg_sq = torch.zeros_like(flat_like)
         elif self.name == "rmsprop":
             self.exp_avg_sq = torch.zeros_like(flat_like)
+            if self.momentum:
+                self.exp_avg = torch.zeros_like(flat_like)   # momentum_buffer
 
     def zero_grad(self):
         """No-op: the HIP optimizer kernels clear the gradient buffer as they consume it."""

@@ -52,6 +52,10 @@ extern "C" {
 #define HIPREC_OPT_SGD 0
 #define HIPREC_OPT_ADAM 1
 #define HIPREC_OPT_RMSPROP 2
+/* torch.optim.RMSprop(momentum = mu > 0), what cmn.py:147-149 builds: square_avg as HIPREC_OPT_RMSPROP, then
+ * buf = mu buf + g / (sqrt(square_avg) + eps); w -= lr buf.  Taken by hiprec_opt_dense_step and
+ * hiprec_clip_opt_dense_step only: m holds buf, v holds square_avg, beta1 carries mu, beta2 alpha. */
+#define HIPREC_OPT_RMSPROP_MOMENTUM 3
 
 /* The five parameter tensors of beta_rec/models/mf.py:21-25 (MF.__init__), or any buffer set of
  * the same shape (gradient accumulators).  Row-major fp32. */
@@ -1143,6 +1147,67 @@ int hiprec_clip_opt_dense_step(int kind, float* w, float* g, float* m, float* v,
                                double beta2, double eps, hiprec_stats* stats, const void* scratch,
                                int64_t scalar_index, float max_norm, void* workspace, size_t workspace_bytes,
                                void* stream);
+
+/* ================= CMN, the Collaborative Memory Network =====================
+ * models/cmn.py:12-61 parameters in named_parameters() order, which is also the order of the ONE flat buffer the
+ * host keeps them in (and of the dense gradient):  user_memory M [n_users, dim], item_memory E [n_items, dim],
+ * user_output C [n_users, dim], mem_layer.hop_mapping.1 weight W [dim, dim] / bias b [dim], dense weight
+ * Wd [dim, 2 dim] / bias bd [dim], out weight w [dim]. */
+typedef struct hiprec_cmn_tables {
+  float* user_memory; /* [n_users, dim] */
+  float* item_memory; /* [n_items, dim] */
+  float* user_output; /* [n_users, dim] */
+  float* hop_w;       /* [dim, dim] */
+  float* hop_b;       /* [dim] */
+  float* dense_w;     /* [dim, 2 dim] */
+  float* dense_b;     /* [dim] */
+  float* out_w;       /* [dim] */
+  int64_t n_users;    /* < 2^31 */
+  int64_t n_items;
+  int32_t dim;        /* 4 .. 256 */
+  int32_t _pad;
+} hiprec_cmn_tables;
+size_t hiprec_cmn_tables_bytes(void);
+
+/* bytes of device workspace a hiprec_cmn_grad_* call on up to max_batch samples needs (per-query vectors of the dense
+ * layers' gradients: 2 max_batch rows of t, z0, dh, ds h [dim] and [M[u] * E[i] ; o1] [2 dim], + column-sum partials) */
+size_t hiprec_cmn_workspace_bytes(int32_t dim, int64_t max_batch);
+
+/* ---- zero_grad + forward + loss + backward of cmnEngine.train_single_batch (cmn.py:153-196) on `batch` samples
+ * (u, i+, i-, N+, N-), i.e. 2 batch queries (u, i, N = n_1 .. n_L, L >= 1):
+ *   z0 = M[u] + E[i];  hop k = 0, 1: a_j = z_k . M[n_j], p = softmax_j(a), o_k = sum_j p_j C[n_j];
+ *   z1 = relu(W z0 + b + o0);  h = relu(Wd [M[u] * E[i] ; o1] + bd);  s = w . h
+ *   loss = mean(-log(sigmoid(s+ - s-) + 1e-12)) * (inv_batch * batch) + l2_lambda * ||W||_2
+ * Accumulates into the dense gradient g (zeroed by the previous optimizer sweep), leaves the loss partials in scratch
+ * and advances the step counter.  g == NULL: forward only -- pos_scores[batch] (and neg_scores[batch] unless NULL:
+ * cmn.py's forward(evaluation=True)) are written, nothing else; scratch / workspace may then be NULL.
+ * A neighbour list is (pointer to ids, length):
+ *   _padded  pos_nbr [batch, pos_lpad] / pos_len [batch] (likewise neg_*): row b's first len[b] ids
+ *   _csr     an item -> users CSR with one row per item (rowptr [n_items + 1], col): the list of item i is
+ *            col[rowptr[i] .. rowptr[i + 1]), in that order
+ * A user / item / neighbour id out of range or a length outside [1, lpad] sets the status bits; that sample (or list
+ * slot) is skipped. */
+int hiprec_cmn_grad_padded(const hiprec_cmn_tables* w, const hiprec_cmn_tables* g, const int64_t* users,
+                           const int64_t* pos, const int64_t* neg, const int64_t* pos_nbr, const int64_t* pos_len,
+                           int64_t pos_lpad, const int64_t* neg_nbr, const int64_t* neg_len, int64_t neg_lpad,
+                           int64_t batch, float inv_batch, float l2_lambda, float* pos_scores, float* neg_scores,
+                           hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int hiprec_cmn_grad_csr(const hiprec_cmn_tables* w, const hiprec_cmn_tables* g, const int64_t* users,
+                        const int64_t* pos, const int64_t* neg, const int64_t* rowptr, const int64_t* col,
+                        int64_t batch, float inv_batch, float l2_lambda, float* pos_scores, float* neg_scores,
+                        hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
+/* ---- cmnEngine.train_an_epoch (cmn.py:202-267) over resident (user, pos, neg) arrays in visiting order (n_triples,
+ * last batch short), the lists from the CSR: per batch hiprec_cmn_grad_csr and hiprec_clip_opt_dense_step over the flat
+ * buffers that w / g point into, enqueued back to back with no host work in between.  workspace: for `batch`. */
+int hiprec_cmn_epoch(const hiprec_cmn_tables* w, const hiprec_cmn_tables* g, const int64_t* users, const int64_t* pos,
+                     const int64_t* neg, const int64_t* rowptr, const int64_t* col, int64_t n_triples, int64_t batch,
+                     float l2_lambda, float max_norm, int kind, double lr, double beta1, double beta2, double eps,
+                     float* flat_w, float* flat_g, float* flat_m, float* flat_v, int64_t n_flat, hiprec_stats* stats,
+                     void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes,
+                     void* clip_workspace, size_t clip_workspace_bytes, void* stream);
 
 /* ================= Triple2vec (sibling models) ===============================
  * models/triple2vec.py:11-34 parameters.  item_emb2 may be the SAME pointer as item_emb1 (in w and in
