@@ -674,6 +674,22 @@ def lazy_scalars_table(opt, device, cap=LAZY_SCALARS_CAP):
     return table
 
 
+def lazy_state(model, g_flat, opt, device, cap=LAZY_SCALARS_CAP):
+    """The lazy Adam / RMSprop state of an MF model (or a shard of one): the per-row stamps (-1 = never touched; at
+    least one element, a shard may hold no rows), Adam's per-step scalars table, the ``dirty`` flag of a pending
+    flush, and ``c``: the C struct that names them next to w / g / m / v."""
+    import torch
+
+    lz = {"stamp_u": torch.full((max(model.n_users, 1),), -1, dtype=torch.int32, device=device),
+          "stamp_i": torch.full((max(model.n_items, 1),), -1, dtype=torch.int32, device=device),
+          "scalars": lazy_scalars_table(opt, device, cap), "dirty": False}   # raises for betas it cannot tabulate
+    lz["c"] = LazyState(
+        model.flat.data_ptr(), g_flat.data_ptr(), opt.exp_avg.data_ptr() if opt.exp_avg is not None else None,
+        opt.exp_avg_sq.data_ptr(), model.n_users, model.n_items, model.emb_dim, opt.kind, lz["stamp_u"].data_ptr(),
+        lz["stamp_i"].data_ptr(), lz["scalars"].data_ptr(), cap, 0, opt.lr, opt.beta1, opt.beta2, opt.eps)
+    return lz
+
+
 def grow(buf, numel, dtype, device):
     """A work-space tensor of at least `numel` elements: `buf` if it is big enough (same device / dtype), else a new one.
     (Staging buffers are allocated once and kept, not re-made every epoch.)"""

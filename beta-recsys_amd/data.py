@@ -19,8 +19,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._stats import _new_stats, raise_on_status, read_stats
 from .eval import DEFAULT_ITEM_COL, DEFAULT_RATING_COL, DEFAULT_USER_COL, _column, _resolve_device
-from .mf import DeviceTripleBatcher, _new_stats, raise_on_status, read_stats
+from .mf import DeviceTripleBatcher
 
 
 def _draw_seed():

@@ -2,7 +2,8 @@
 
 ``_FlatModel`` keeps every parameter of a model in ONE flat fp32 buffer; ``FlatModelEngine`` serves the engines that
 train such a model: LightGCN, NGCF, PairwiseGMF, Triple2vec and UltraGCN, whose step is ``<model>_grad`` + a dense
-optimizer sweep over that buffer, and NeuMF / GMF / MLP (``ncf.py``), whose step is the one call ``hiprec_ncf_step``.
+optimizer sweep over that buffer, NeuMF / GMF / MLP (``ncf.py``), whose step is the one call ``hiprec_ncf_step``, and
+MF (``mf.py``), which adds its resident-epoch drivers, the touched-rows SGD and the lazy Adam / RMSprop state.
 
 Nothing here has a counterpart in the reference (it has no such layer): the subclasses mirror
 ``beta_rec.models.*Engine``; this base only owns the device-side step state (dense gradient, optimizer
@@ -14,7 +15,7 @@ import torch.nn as nn
 from torch.nn import Parameter
 
 from . import _lib
-from .mf import _new_stats, clear_status, raise_on_status, read_stats
+from ._stats import _new_stats, clear_status, raise_on_status, read_stats
 from .torch_engine import ModelEngine
 
 
@@ -144,19 +145,24 @@ class FlatModelEngine(ModelEngine):
         """How many leading floats of the flat buffers the optimizer moves (all of them by default)."""
         return self.model.flat.numel()
 
-    def _enqueue_opt(self, fold_partials=True):
+    def _enqueue_opt(self, fold_partials=True, scalar_index=-1):
         """optimizer.step(): the dense sweep, which also folds the loss partials into the stats (unless the caller
-        has done that already) and leaves the gradient cleared."""
+        has done that already) and leaves the gradient cleared.  ``scalar_index``: the element whose gradient travels
+        in those partials (MF's ``global_bias``), -1 for none."""
         lib, m, opt = _lib.load(), self.model, self.optimizer
         _lib.check(lib.hiprec_opt_dense_step(
             opt.kind, _lib.ptr(m.flat), _lib.ptr(self._g_flat), _lib.ptr(opt.exp_avg),
             _lib.ptr(opt.exp_avg_sq), self._sweep_floats(), opt.lr, opt.beta1, opt.beta2, opt.eps,
-            _lib.ptr(self._stats), _lib.ptr(self._scratch) if fold_partials else None, -1,
+            _lib.ptr(self._stats), _lib.ptr(self._scratch) if fold_partials else None, scalar_index,
             _lib.stream_ptr(m.flat.device)))
 
     def _enqueue_step(self, batch_data):
         self._enqueue_grad(batch_data)
         self._enqueue_opt()
+
+    def _drop_step_state(self):
+        """What a step that skipped flagged rows leaves half-done: the partially accumulated gradient."""
+        self._g_flat.zero_()
 
     def _sync_stats(self):
         """The one host sync of a step / epoch; out-of-range ids surface here as IndexError (the sticky
@@ -164,7 +170,7 @@ class FlatModelEngine(ModelEngine):
         st = read_stats(self._stats)
         if st.status:
             clear_status(self._stats)
-            self._g_flat.zero_()
+            self._drop_step_state()
             raise_on_status(st.status)
         return st
 

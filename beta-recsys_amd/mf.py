@@ -1,6 +1,6 @@
 """Drop-in ``MF`` / ``MFEngine`` for beta_rec/models/mf.py, backed by libhiprec.so (HIP, gfx950).
 
-Interface parity with the reference (file:line = /root/reference/beta_rec/...):
+Interface parity with the reference (file:line = beta_rec/...):
 
 * ``MF(config)``            models/mf.py:12-30  — same config keys, same state_dict keys / shapes,
   same initial weights for the same torch seed (the RNG is consumed in the same order).
@@ -16,42 +16,23 @@ parameter tensors are views into ONE flat fp32 buffer so that the dense optimize
 contiguous range, and so are the gradient accumulator and the optimizer moments.
 """
 import ctypes
-import time
-from functools import wraps
 
 import numpy as np
 import torch
-import torch.nn as nn
 from torch.nn import Parameter
 
 from . import _lib
-from .torch_engine import ModelEngine
+from ._stats import _new_stats, clear_status, raise_on_status, read_stats  # noqa: F401  (re-exported: tests, tools)
+from .flat_engine import FlatModelEngine, _FlatModel, _ParamView
+from .torch_engine import timeit
+
+# Quirk Q4 (mf.py:44): .squeeze() drops the batch dim of a single-sample batch and torch.sum(dim=1) raises; the
+# reference cannot train on a batch of one, and says so with this message.
+_Q4_MESSAGE = "Dimension out of range (expected to be in range of [-1, 0], but got 1)"
 
 
-def timeit(method):
-    """Same console contract as beta_rec/utils/common_util.py:215-245."""
-
-    @wraps(method)
-    def wrapper(*args, **kw):
-        ts = time.time()
-        result = method(*args, **kw)
-        te = time.time()
-        if "log_time" in kw:
-            name = kw.get("log_name", method.__name__.upper())
-            kw["log_time"][name] = int((te - ts) * 1000)
-        else:
-            print("Execute [{}] method costing {:2.2f} ms".format(method.__name__, (te - ts) * 1000))
-        return result
-
-    return wrapper
-
-
-class _Table(nn.Module):
+class _Table(_ParamView):
     """nn.Embedding look-alike whose ``weight`` is a view into the model's flat buffer."""
-
-    def __init__(self, weight_view):
-        super().__init__()
-        self.weight = Parameter(weight_view, requires_grad=False)
 
     @property
     def num_embeddings(self):
@@ -67,54 +48,6 @@ class _Table(nn.Module):
 
     def extra_repr(self):
         return f"{self.num_embeddings}, {self.embedding_dim}"
-
-
-def _new_stats(device, beta1=0.9, beta2=0.999):
-    lib = _lib.load()
-    stats = torch.zeros(ctypes.sizeof(_lib.Stats), dtype=torch.uint8, device=device)
-    _lib.check(lib.hiprec_stats_reset(_lib.ptr(stats), beta1, beta2, _lib.stream_ptr(device)))
-    return stats
-
-
-def read_stats(stats_tensor):
-    """Copy the device hiprec_stats block to the host (synchronises) and decode it."""
-    raw = stats_tensor.cpu().numpy().tobytes()
-    return _lib.Stats.from_buffer_copy(raw)
-
-
-def clear_status(stats):
-    """Zero the 4-byte status word of a device hiprec_stats -- and only that: the struct also holds the optimizer
-    clock and the epoch sums, which kernels of other streams may be advancing (writing back a host copy of
-    the whole struct raced them)."""
-    off = _lib.Stats.status.offset
-    stats[off:off + 4].zero_()
-
-
-def raise_on_status(status):
-    """Turn sticky device status bits into the IndexError PyTorch would have raised."""
-    if status:
-        which = []
-        if status & _lib.STATUS_USER_OOB:
-            which.append("user")
-        if status & _lib.STATUS_ITEM_OOB:
-            which.append("item")
-        if status & _lib.STATUS_ROW_OOB:
-            which.append("row")
-        if status & _lib.STATUS_NEG_EXHAUSTED:
-            raise ValueError("Sample larger than population or is negative")  # random.sample's message
-        if status & _lib.STATUS_LAZY_TABLE:
-            raise RuntimeError(
-                "lazy Adam: the optimizer ran past the bias-correction table while the corrections still moved "
-                "(non-default betas?): use config['model']['dense_opt'] = 'sweep'")
-        if status & _lib.STATUS_TABLE_FULL:
-            raise RuntimeError(
-                "a batch's row-contribution hash partition overflowed while the epoch was staged: the step's lists are "
-                "incomplete (should be impossible at >= 4 table entries per triple; please report the batch)")
-        if status & _lib.STATUS_ROUTE_OVERFLOW:
-            raise RuntimeError(
-                "a fixed-capacity all-to-all bucket overflowed: raise the sharded engine's "
-                "`route_slack` (config['model']['route_slack'])")
-        raise IndexError("index out of range in self (" + "/".join(which) + " index)")
 
 
 _gather_stats = {}
@@ -149,7 +82,7 @@ def gather_rows(table, idx, check=False):
     return out.reshape(*idx.shape, table.shape[1])
 
 
-class MF(nn.Module):
+class MF(_FlatModel):
     """Matrix factorisation model, parameter-compatible with beta_rec/models/mf.py:9-70."""
 
     def __init__(self, config):
@@ -161,9 +94,11 @@ class MF(nn.Module):
         self.n_items = int(self.config["n_items"])
         self.emb_dim = int(self.config["emb_dim"])
         U, I, D = self.n_users, self.n_items, self.emb_dim
-        self._sizes = (U * D, I * D, U, I, 1)
-        flat = torch.empty(sum(self._sizes), dtype=torch.float32)
-        ue, ie, ub, ib, gb = self._views(flat)
+        # the flat fp32 buffer [user_emb | item_emb | user_bias | item_bias | global_bias]: hiprec_mf_tables, the
+        # dense sweep's scalar_index = numel - 1, the fused kernels and the sharded engine rely on this order
+        ue, ie, ub, ib, gb = self._build([
+            ("user_emb.weight", (U, D)), ("item_emb.weight", (I, D)), ("user_bias.weight", (U, 1)),
+            ("item_bias.weight", (I, 1)), ("global_bias", (1,))]).values()
         # Consume the torch RNG exactly like mf.py:21-30: four nn.Embedding constructors draw
         # N(0,1) for their weights, biases are zero-filled, then the two tables are re-drawn.
         ue.normal_(0, 1)
@@ -175,50 +110,16 @@ class MF(nn.Module):
         gb.fill_(0.0)
         ue.normal_(0, self.stddev)
         ie.normal_(0, self.stddev)
-        self._flat = flat
         self._table_cache = {}
         self.user_emb = _Table(ue)
         self.item_emb = _Table(ie)
         self.user_bias = _Table(ub)
         self.item_bias = _Table(ib)
         self.global_bias = Parameter(gb, requires_grad=False)
-        self._stats = None
 
-    # ---- flat-buffer plumbing -------------------------------------------------------------
     def _views(self, flat):
-        U, I, D = self.n_users, self.n_items, self.emb_dim
-        o = np.cumsum((0,) + self._sizes)
-        return (
-            flat[o[0]:o[1]].view(U, D),
-            flat[o[1]:o[2]].view(I, D),
-            flat[o[2]:o[3]].view(U, 1),
-            flat[o[3]:o[4]].view(I, 1),
-            flat[o[4]:o[5]],
-        )
-
-    def _rebind(self, flat):
-        ue, ie, ub, ib, gb = self._views(flat)
-        self._flat = flat
-        self.user_emb.weight.data = ue
-        self.item_emb.weight.data = ie
-        self.user_bias.weight.data = ub
-        self.item_bias.weight.data = ib
-        self.global_bias.data = gb
-
-    def _apply(self, fn, recurse=True):
-        """``.to() / .cuda() / .float()``: move the flat buffer once and re-point the views."""
-        new_flat = fn(self._flat)
-        if new_flat.dtype != torch.float32:
-            raise TypeError("hiprec MF keeps fp32 parameters (the reference trains in fp32)")
-        if new_flat is not self._flat:
-            self._rebind(new_flat.contiguous())
-            self._stats = None
-        return self
-
-    @property
-    def flat(self):
-        """The flat fp32 buffer [user_emb | item_emb | user_bias | item_bias | global_bias]."""
-        return self._flat
+        """``views(flat)`` as a tuple in layout order: ``(user_emb, item_emb, user_bias, item_bias, global_bias)``."""
+        return tuple(self.views(flat).values())
 
     def tables(self, flat=None):
         """hiprec_mf_tables over this model's layout (``flat`` defaults to the parameters)."""
@@ -226,24 +127,12 @@ class MF(nn.Module):
         base = flat.data_ptr()
         cached = self._table_cache.get(base)
         if cached is None:
-            o = np.cumsum((0,) + self._sizes) * 4
-            cached = _lib.MfTables(
-                base + int(o[0]), base + int(o[1]), base + int(o[2]), base + int(o[3]),
-                base + int(o[4]), self.n_users, self.n_items, self.emb_dim, 0)
+            cached = _lib.MfTables(*(base + 4 * int(o) for o in self._offsets[:5]),
+                                   self.n_users, self.n_items, self.emb_dim, 0)
             if len(self._table_cache) > 8:
                 self._table_cache.clear()
             self._table_cache[base] = cached
         return cached
-
-    def _require_hip(self):
-        if self._flat.device.type != "cuda":
-            raise RuntimeError(
-                "hiprec MF computes on an MI355X through libhiprec.so only; parameters are on "
-                f"{self._flat.device} and there is deliberately no CPU fallback"
-            )
-        if self._stats is None:
-            self._stats = _new_stats(self._flat.device)
-        return _lib.load()
 
     # ---- reference API ---------------------------------------------------------------------
     def forward(self, batch_data):
@@ -260,12 +149,9 @@ class MF(nn.Module):
         scores, sq = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
         tabs = self.tables()
         _lib.check(lib.hiprec_mf_forward(ctypes.byref(tabs), _lib.ptr(users), _lib.ptr(items), n, _lib.ptr(scores),
-                                         _lib.ptr(sq), _lib.ptr(self._stats), _lib.stream_ptr(dev)))
+                                         _lib.ptr(sq), _lib.ptr(self._device_stats()), _lib.stream_ptr(dev)))
         # nn.Embedding raises IndexError for an id outside its table (mf.py:41-42); the kernel flags it (NaN score)
-        st = read_stats(self._stats)
-        if st.status:
-            clear_status(self._stats)
-            raise_on_status(st.status)
+        self._check_status()
         return scores, sq.sum() / max(n, 1)
 
     def _scores(self, users, items):
@@ -279,7 +165,7 @@ class MF(nn.Module):
         _lib.check(
             lib.hiprec_mf_predict(
                 ctypes.byref(tabs), _lib.ptr(users), _lib.ptr(items), n, _lib.ptr(scores),
-                _lib.ptr(self._stats), _lib.stream_ptr(dev),
+                _lib.ptr(self._device_stats()), _lib.stream_ptr(dev),
             )
         )
         return scores
@@ -298,11 +184,7 @@ class MF(nn.Module):
         users_t = torch.as_tensor(np.asarray(users), dtype=torch.int64).to(dev).contiguous()
         items_t = torch.as_tensor(np.asarray(items), dtype=torch.int64).to(dev).contiguous()
         scores = self._scores(users_t.reshape(-1), items_t.reshape(-1))
-        st = read_stats(self._stats)
-        if st.status:
-            _lib.check(_lib.load().hiprec_stats_reset(_lib.ptr(self._stats), 0.9, 0.999,
-                                                      _lib.stream_ptr(dev)))
-            raise_on_status(st.status)
+        self._check_status()
         return scores
 
 
@@ -525,7 +407,7 @@ def _print_config_table(config, tag):
     print("-" * 80)
 
 
-class MFEngine(ModelEngine):
+class MFEngine(FlatModelEngine):
     """Engine with the surface of beta_rec/models/mf.py:73-139, computing through libhiprec."""
 
     # SGD keeps every untouched row bit-identical, so it may either sweep the whole flat buffer
@@ -547,20 +429,11 @@ class MFEngine(ModelEngine):
         self.model.to(self.device)
         self.loss = self.config["model"]["loss"] if "loss" in self.config["model"] else "bpr"
         print(f"using {self.loss} loss...")
-        self._buffers_ready = False
         self._stamp = 1
 
     # ---- buffers ---------------------------------------------------------------------------
-    def _setup(self):
-        lib = self.require_hip()
-        if self._buffers_ready and self._g_flat.device == self.model.flat.device:
-            return lib
+    def _alloc_extra(self, lib, dev):
         flat = self.model.flat
-        dev = flat.device
-        self._g_flat = torch.zeros_like(flat)
-        self.optimizer.allocate_state(flat)
-        self._scratch = torch.zeros(lib.hiprec_scratch_bytes(0), dtype=torch.uint8, device=dev)
-        self._stats = _new_stats(dev, self.optimizer.beta1 or 0.9, self.optimizer.beta2 or 0.999)
         # plain SGD on tables beyond the caches visits only the rows of the step.  sgd_mode: "dense" (sweep),
         # "rows" (dense gradient buffer + touched-rows pass, two kernels), "owned" (resident BPR epochs run the
         # one-launch in-place step of csrc/mf_owned.hip, everything else as "rows"), "auto" = dense below 64 MB
@@ -583,18 +456,7 @@ class MFEngine(ModelEngine):
         if (self.optimizer.name != "sgd" and self.model.emb_dim <= 256 and self._lazy_capable
                 and (mode == "lazy" or (mode == "auto" and flat.numel() * 4 >= self.ROWS_SGD_MIN_BYTES
                                         and _lib.lazy_betas_converge(self.optimizer)))):   # auto: else the sweep
-            opt, m = self.optimizer, self.model
-            lz = {"stamp_u": torch.full((m.n_users,), -1, dtype=torch.int32, device=dev),
-                  "stamp_i": torch.full((m.n_items,), -1, dtype=torch.int32, device=dev),
-                  "scalars": _lib.lazy_scalars_table(opt, dev), "dirty": False}   # raises for betas it cannot tabulate
-            lz["c"] = _lib.LazyState(
-                flat.data_ptr(), self._g_flat.data_ptr(), opt.exp_avg.data_ptr() if opt.exp_avg is not None else None,
-                opt.exp_avg_sq.data_ptr(), m.n_users, m.n_items, m.emb_dim, opt.kind, lz["stamp_u"].data_ptr(),
-                lz["stamp_i"].data_ptr(), lz["scalars"].data_ptr(), _lib.LAZY_SCALARS_CAP, 0, opt.lr, opt.beta1,
-                opt.beta2, opt.eps)
-            self._lazy = lz
-        self._buffers_ready = True
-        return lib
+            self._lazy = _lib.lazy_state(self.model, self._g_flat, self.optimizer, dev)
 
     _lazy_capable = True    # (the data-parallel replicas always sweep: their gradient is dense after the all-reduce)
 
@@ -653,9 +515,7 @@ class MFEngine(ModelEngine):
         if B == 0:
             raise ValueError("empty batch")
         if B == 1:
-            # Quirk Q4 (mf.py:44): .squeeze() drops the batch dim of a single-sample batch and
-            # torch.sum(dim=1) raises; the reference cannot train on a batch of one.
-            raise IndexError("Dimension out of range (expected to be in range of [-1, 0], but got 1)")
+            raise IndexError(_Q4_MESSAGE)
         return users, a_items, third
 
     def _enqueue_grad(self, lib, users, a_items, third):
@@ -687,12 +547,13 @@ class MFEngine(ModelEngine):
                 _lib.ptr(self._item_stamp), self._take_stamps(1), _lib.ptr(self._stats),
                 _lib.ptr(self._scratch), st))
         else:
-            self.flush_lazy()   # (pieces of a lazy epoch may be pending)
-            _lib.check(lib.hiprec_opt_dense_step(
-                opt.kind, _lib.ptr(m.flat), _lib.ptr(self._g_flat), _lib.ptr(opt.exp_avg),
-                _lib.ptr(opt.exp_avg_sq), m.flat.numel(), opt.lr, opt.beta1, opt.beta2, opt.eps,
-                _lib.ptr(self._stats), _lib.ptr(self._scratch), m.flat.numel() - 1, st))
-            self._lazy_mark_current()
+            self._enqueue_opt()
+
+    def _enqueue_opt(self, fold_partials=True):
+        """The dense sweep; the gradient of ``global_bias`` (the buffer's last element) travels in the loss partials."""
+        self.flush_lazy()   # (pieces of a lazy epoch may be pending)
+        super()._enqueue_opt(fold_partials, scalar_index=self.model.flat.numel() - 1)
+        self._lazy_mark_current()
 
     def backward_only(self, batch_data):
         """zero_grad + forward + backward WITHOUT the optimizer step (what autograd leaves in
@@ -700,41 +561,17 @@ class MFEngine(ModelEngine):
         keyed like ``state_dict``; the accumulator is cleared again afterwards.  Note that like
         every grad call it advances the optimizer clock by one."""
         users, a_items, third = self._prepare_batch(batch_data)
-        lib = self._setup()
-        self._enqueue_grad(lib, users, a_items, third)
-        g_global = self.model._views(self._g_flat)[4]
-        _lib.check(lib.hiprec_finalize_stats(
-            _lib.ptr(self._stats), _lib.ptr(self._scratch), _lib.ptr(g_global), None,
-            _lib.stream_ptr(self.model.flat.device)))
-        st = self._sync_stats()
-        ue, ie, ub, ib, gb = (v.clone() for v in self.model._views(self._g_flat))
-        self._g_flat.zero_()
-        grads = {"global_bias": gb, "user_emb.weight": ue, "item_emb.weight": ie,
-                 "user_bias.weight": ub, "item_bias.weight": ib}
+        self._enqueue_grad(self._setup(), users, a_items, third)
+        # d loss / d global_bias travels in the scratch partials: the reduction puts it into its gradient slot
+        st, grads = self._finish_backward_only(_lib.ptr(self.model.views(self._g_flat)["global_bias"]))
         return st.loss, st.reg, grads
 
     def load_optimizer_state(self, step, exp_avg=None, exp_avg_sq=None):
         """Restore the optimizer clock and moments (the reference never persists them —
         torch_engine.py:70-73 — so this is an extension used for resume and for tests).
         ``exp_avg`` / ``exp_avg_sq`` are dicts keyed like ``state_dict`` (or None for zeros)."""
-        lib = self._setup()
-        opt, m = self.optimizer, self.model
-        dev = m.flat.device
-        _lib.check(lib.hiprec_stats_reset(
-            _lib.ptr(self._stats), opt.beta1 or 0.9, opt.beta2 or 0.999, _lib.stream_ptr(dev)))
-        _lib.check(lib.hiprec_stats_set_step(_lib.ptr(self._stats), int(step), opt.beta1 or 0.9,
-                                             opt.beta2 or 0.999, _lib.stream_ptr(dev)))
-        for buf, src in ((opt.exp_avg, exp_avg), (opt.exp_avg_sq, exp_avg_sq)):
-            if buf is None:
-                continue
-            if src is None:
-                buf.zero_()
-                continue
-            ue, ie, ub, ib, gb = m._views(buf)
-            for view, key in ((gb, "global_bias"), (ue, "user_emb.weight"), (ie, "item_emb.weight"),
-                              (ub, "user_bias.weight"), (ib, "item_bias.weight")):
-                view.copy_(torch.as_tensor(src[key], dtype=torch.float32).reshape(view.shape))
-        if getattr(self, "_lazy", None) is not None:
+        super().load_optimizer_state(step, exp_avg, exp_avg_sq)
+        if self._lazy is not None:
             self._lazy["dirty"] = False
             self._lazy_mark_current()   # whatever was loaded is current as of the restored clock
 
@@ -743,28 +580,17 @@ class MFEngine(ModelEngine):
         self._setup()
         self.flush_lazy()
         st = read_stats(self._stats)
-        out = []
-        for buf in (self.optimizer.exp_avg, self.optimizer.exp_avg_sq):
-            if buf is None:
-                out.append(None)
-                continue
-            ue, ie, ub, ib, gb = self.model._views(buf)
-            out.append({"global_bias": gb.clone(), "user_emb.weight": ue.clone(),
-                        "item_emb.weight": ie.clone(), "user_bias.weight": ub.clone(),
-                        "item_bias.weight": ib.clone()})
-        return st.step, out[0], out[1]
+        exp_avg, exp_avg_sq = (
+            None if buf is None else {k: v.clone() for k, v in self.model.views(buf).items()}
+            for buf in (self.optimizer.exp_avg, self.optimizer.exp_avg_sq))
+        return st.step, exp_avg, exp_avg_sq
 
-    def _sync_stats(self):
-        st = read_stats(self._stats)
-        if st.status:
-            # clear the sticky bits, keep the optimizer clock
-            clear_status(self._stats)
-            ob = getattr(self, "_owned_bufs", None)
-            if ob is not None:   # a skipped (out-of-range) triple leaves its rows' counts incomplete
-                ob["arrived"].zero_()
-                ob["acc"].zero_()
-            raise_on_status(st.status)
-        return st
+    def _drop_step_state(self):
+        super()._drop_step_state()
+        ob = getattr(self, "_owned_bufs", None)
+        if ob is not None:   # a skipped (out-of-range) triple leaves its rows' counts incomplete
+            ob["arrived"].zero_()
+            ob["acc"].zero_()
 
     def train_single_batch(self, batch_data):
         """mf.py:92-119: one optimisation step; returns ``(loss, regularizer)`` floats."""
@@ -1092,37 +918,42 @@ class MFEngine(ModelEngine):
             self._begin_epoch_marker(prepared, prefetch)
         if self._owned_sgd and self.loss == "bpr" and getattr(prepared, "own", None) is not None:
             self._run_owned_epoch(lib, prepared, n_run, steps)
-            if not sync:
-                return None
-            st = self._sync_stats()
-            if n_run != n:
-                raise IndexError(
-                    "Dimension out of range (expected to be in range of [-1, 0], but got 1)")
-            return st
+            return self._epoch_result(sync, n_run != n)
         if self._lazy is not None and perm is None and self.loss in ("bpr", "bce"):
             self._run_lazy_epoch(lib, users, pos, neg, n_run, bs, steps, getattr(prepared, "own", None))
-            if not sync:
-                return None
-            st = self._sync_stats()
-            if n_run != n:
-                raise IndexError(
-                    "Dimension out of range (expected to be in range of [-1, 0], but got 1)")
-            return st
+            return self._epoch_result(sync, n_run != n)
         if self._fused_ok(perm):
             self._run_fused_epoch(lib, users, pos, neg, n_run, bs, steps)
-            if not sync:
-                return None
-            st = self._sync_stats()
-            if n_run != n:
-                raise IndexError(
-                    "Dimension out of range (expected to be in range of [-1, 0], but got 1)")
-            return st
+            return self._epoch_result(sync, n_run != n)
         if steps is not None:
             # the launch-per-kernel drivers keep no state between steps: a piece is a slice of the arrays
             a, b = steps[0] * bs, min(steps[1] * bs, n_run)
             users, pos, neg, n_run = users[a:b], pos[a:b], neg[a:b], b - a
             perm = None if perm is None else perm[a:b]
         return self._run_unfused_epoch(lib, users, pos, neg, perm, bs, n, n_run, sync)
+
+    def _epoch_result(self, sync, short_tail):
+        """How every form of the epoch ends: nothing when the caller syncs later, else the stats -- after quirk Q4's
+        error when the epoch's trailing batch of one was left out (``short_tail``)."""
+        if not sync:
+            return None
+        st = self._sync_stats()
+        if short_tail:
+            raise IndexError(_Q4_MESSAGE)
+        return st
+
+    def _pull_workspace(self, cap):
+        """The owner-pulls steps' contribution buffer: ``cap`` rows (+ biases), one per row occurrence of a batch at
+        worst; plain stores, never cleared, kept and grown across epochs."""
+        dev, dim = self.model.flat.device, self.model.emb_dim
+        pb = getattr(self, "_pull_bufs", None)
+        if pb is None or pb["dev"] != dev or pb["cap"] < cap:
+            pb = self._pull_bufs = {
+                "dev": dev, "cap": cap,
+                "cbuf": torch.empty(cap * dim, dtype=torch.float32, device=dev),
+                "cbias": torch.empty(cap, dtype=torch.float32, device=dev),
+                "scratch": torch.zeros_like(self._scratch)}
+        return pb
 
     def _run_lazy_epoch(self, lib, users, items_a, third, n_run, bs, steps, own=None):
         """hiprec_mf_epoch_lazy (csrc/lazy_opt.hip): per step catch-up of the batch's rows, the gradient kernel, the
@@ -1138,14 +969,7 @@ class MFEngine(ModelEngine):
         if isinstance(own, RowContributions) and self.loss == "bpr" and self._lazy_owned() == "pull":
             cidx, rows, counts, row_cap = own
             n_all = cidx.shape[1]
-            cap = 3 * min(bs, max(n_all, 1))
-            pb = getattr(self, "_pull_bufs", None)
-            if pb is None or pb["dev"] != m.flat.device or pb["cap"] < cap:
-                pb = self._pull_bufs = {
-                    "dev": m.flat.device, "cap": cap,
-                    "cbuf": torch.empty(cap * m.emb_dim, dtype=torch.float32, device=m.flat.device),
-                    "cbias": torch.empty(cap, dtype=torch.float32, device=m.flat.device),
-                    "scratch": torch.zeros_like(self._scratch)}
+            pb = self._pull_workspace(3 * min(bs, max(n_all, 1)))
             _lib.check(lib.hiprec_mf_epoch_lazy_pull(
                 ctypes.byref(lz["c"]), ctypes.c_void_p(users.data_ptr() + 8 * lo),
                 ctypes.c_void_p(items_a.data_ptr() + 8 * lo), ctypes.c_void_p(third.data_ptr() + 8 * lo),
@@ -1212,14 +1036,7 @@ class MFEngine(ModelEngine):
         m = self.model
         dev = m.flat.device
         n = users.numel()
-        cap = 3 * min(bs, max(n, 1))
-        pb = getattr(self, "_pull_bufs", None)
-        if pb is None or pb["dev"] != dev or pb["cap"] < cap:
-            pb = self._pull_bufs = {
-                "dev": dev, "cap": cap,
-                "cbuf": torch.empty(cap * m.emb_dim, dtype=torch.float32, device=dev),
-                "cbias": torch.empty(cap, dtype=torch.float32, device=dev),
-                "scratch": torch.zeros_like(self._scratch)}
+        pb = self._pull_workspace(3 * min(bs, max(n, 1)))
         n_steps = (n_run + bs - 1) // bs
         a, b = (0, n_steps) if steps is None else steps
         _lib.check(lib.hiprec_mf_bpr_epoch_pull(
@@ -1251,13 +1068,7 @@ class MFEngine(ModelEngine):
             _lib.ptr(opt.exp_avg_sq), m.flat.numel(), _lib.ptr(self._user_stamp),
             _lib.ptr(self._item_stamp), first, _lib.ptr(self._stats),
             _lib.ptr(self._scratch), self._scratch.numel(), _lib.stream_ptr(m.flat.device)))
-        if not sync:
-            return None
-        st = self._sync_stats()
-        if n_run != n:
-            raise IndexError(
-                "Dimension out of range (expected to be in range of [-1, 0], but got 1)")
-        return st
+        return self._epoch_result(sync, n_run != n)
 
     def epoch_stats(self):
         """Synchronise and return the device statistics (loss, reg, loss_sum, reg_sum, step)."""
@@ -1268,22 +1079,15 @@ class MFEngine(ModelEngine):
         """mf.py:121-139.  One host sync per epoch instead of two per step."""
         assert hasattr(self, "model"), "Please specify the exact model !"
         self.model.train()
-        lib = self._setup()
+        self._setup()
         prepared = self.prepare_epoch(train_loader)
         if prepared is not None:
-            # the next epoch's shuffle + staging overlaps this one (side stream)
+            # the next epoch's shuffle + staging overlaps this one (side stream); Q4: a trailing batch of one raises
+            # in the reference, here after the epoch's other steps have run
             ahead = train_loader if self.config["model"].get("prefetch_epoch", True) else None
-            self.run_prepared_epoch(prepared, sync=False, prefetch=ahead)
-            n, bs = prepared[0].numel(), prepared[4]
-            st = self._sync_stats()
-            if n % bs == 1:  # Q4: a trailing batch of one raises in the reference
-                raise IndexError("Dimension out of range (expected to be in range of [-1, 0], but got 1)")
+            st = self.run_prepared_epoch(prepared, prefetch=ahead)
         else:
-            _lib.check(lib.hiprec_stats_begin_epoch(
-                _lib.ptr(self._stats), _lib.stream_ptr(self.model.flat.device)))
-            for batch_data in train_loader:
-                self._enqueue_step(batch_data)
-            st = self._sync_stats()
+            st = self._run_epoch(train_loader)
         loss, total_loss, regularizer = st.loss, st.loss_sum, st.reg_sum
         print(f"[Training Epoch {epoch_id}], Loss {loss}, Regularizer {regularizer}")
         self.writer.add_scalar("model/loss", total_loss, epoch_id)

@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import _lib
 from .flat_engine import FlatModelEngine, _FlatModel, _ParamView, index_tensor
-from .mf import timeit
+from .torch_engine import timeit
 
 
 def _tower_dims(emb_dim, n_layers):

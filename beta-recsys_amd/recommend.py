@@ -11,9 +11,9 @@ CPU fallback: the arithmetic runs in libhiprec.so on the GPU or not at all.
 import torch
 
 from . import _lib
+from ._stats import _new_stats, clear_status, raise_on_status, read_stats
 from .data import build_positive_csr
 from .flat_engine import index_tensor
-from .mf import _new_stats, clear_status, raise_on_status, read_stats
 
 MAX_K = 128        # HIPREC_TOPK_MAX_K
 MAX_DIM = 512      # HIPREC_TOPK_MAX_DIM

@@ -70,7 +70,7 @@ class ReplicatedMFEngine(MFEngine):
             dist.broadcast(self.model.flat, src=0, group=self.pg)
 
     def _setup(self):
-        fresh = not self._buffers_ready
+        fresh = not self._ready
         lib = super()._setup()
         if fresh or self._g_ext.device != self.model.flat.device:
             P = self.model.flat.numel()

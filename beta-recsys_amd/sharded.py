@@ -31,7 +31,8 @@ import torch
 from . import _dist as dist
 
 from . import _lib
-from .mf import MF, _new_stats, clear_status, raise_on_status, read_stats
+from ._stats import _new_stats, clear_status, raise_on_status, read_stats
+from .mf import MF
 from .torch_engine import HipOptimizer
 
 KEYS = ("global_bias", "user_emb.weight", "item_emb.weight", "user_bias.weight", "item_bias.weight")
@@ -314,22 +315,7 @@ class HipKernels:
             _lib.SHARD_EXCHANGE_SELF if self_exchange else 0, _lib.ptr(self.stats), self._st()))
 
     # ---- exact lazy Adam / RMSprop (csrc/lazy_opt.hip) -------------------------------------------------------------
-    LAZY_SCALARS = _lib.LAZY_SCALARS_CAP     # steps whose bias corrections are tabulated (default betas converge by t ~ 36 800)
-
-    def lazy_state(self, model, g_flat, opt):
-        """The per-row stamps (-1 = never touched) and Adam's per-step scalars table of a shard, with the C struct
-        that names them next to w / g / m / v."""
-        dev = self.device
-        lz = {"stamp_u": torch.full((max(model.n_users, 1),), -1, dtype=torch.int32, device=dev),
-              "stamp_i": torch.full((max(model.n_items, 1),), -1, dtype=torch.int32, device=dev),
-              "scalars": _lib.lazy_scalars_table(opt, dev, self.LAZY_SCALARS), "dirty": False}
-        lz["c"] = _lib.LazyState(
-            model.flat.data_ptr(), g_flat.data_ptr(), opt.exp_avg.data_ptr() if opt.exp_avg is not None else None,
-            opt.exp_avg_sq.data_ptr(), model.n_users, model.n_items, model.emb_dim, opt.kind, lz["stamp_u"].data_ptr(),
-            lz["stamp_i"].data_ptr(), lz["scalars"].data_ptr(), self.LAZY_SCALARS, 0, opt.lr, opt.beta1, opt.beta2,
-            opt.eps)
-        return lz
-
+    # (the state itself -- stamps, scalars table, C struct -- is _lib.lazy_state's)
     @staticmethod
     def _lazy_rows(users, items32):
         return _lib.LazyRows(users.data_ptr(), users.numel(), None, 0, None, 0, items32.data_ptr(), items32.numel())
@@ -440,7 +426,7 @@ class ShardedMFEngine:
         if (self.optimizer.name != "sgd" and isinstance(self.k, HipKernels) and self.emb_dim <= 256
                 and (mode == "lazy" or (mode == "auto" and self.model.flat.numel() * 4 >= (64 << 20)
                                         and _lib.lazy_betas_converge(self.optimizer)))):
-            self._lazy = self.k.lazy_state(self.model, self._g_flat, self.optimizer)
+            self._lazy = _lib.lazy_state(self.model, self._g_flat, self.optimizer, self.device)
         # "padded": fixed-capacity all-to-alls, bucketing on the device, no host sync per step (all
         # ranks must feed the same local batch size); "variable": exact-size all-to-alls with
         # host-side split sizes (any batch sizes, one host sync per exchange)

@@ -30,7 +30,7 @@ from . import _dist as dist
 
 from . import _lib
 from . import ncf as ncf_mod
-from .mf import _new_stats, clear_status, raise_on_status, read_stats
+from ._stats import _new_stats, clear_status, raise_on_status, read_stats
 from .sharded import shard_rows
 from .torch_engine import HipOptimizer
 

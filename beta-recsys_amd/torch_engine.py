@@ -7,10 +7,31 @@ Same constructor contract, attributes (``model optimizer device writer config``)
 thin descriptor: the arithmetic of ``torch.optim.{SGD,Adam,RMSprop}.step`` runs in
 ``csrc/optim.hip`` on flat state buffers owned here.
 """
+import time
+from functools import wraps
+
 import torch
 import torch.nn.functional as F
 
 from . import _lib
+
+
+def timeit(method):
+    """Same console contract as beta_rec/utils/common_util.py:215-245."""
+
+    @wraps(method)
+    def wrapper(*args, **kw):
+        ts = time.time()
+        result = method(*args, **kw)
+        te = time.time()
+        if "log_time" in kw:
+            name = kw.get("log_name", method.__name__.upper())
+            kw["log_time"][name] = int((te - ts) * 1000)
+        else:
+            print("Execute [{}] method costing {:2.2f} ms".format(method.__name__, (te - ts) * 1000))
+        return result
+
+    return wrapper
 
 
 class _NullWriter:

@@ -228,6 +228,20 @@ def test_parameters_are_views_of_one_flat_buffer():
         m.half()
     t = m.tables()
     assert (t.n_users, t.n_items, t.dim) == (U, I, D) and t.user_emb == m.flat.data_ptr()
+    # the model sits on the flat-model base: one spec states the layout, `_views` is its positional form
+    import inspect
+
+    from beta_recsys_amd import flat_engine
+
+    assert isinstance(m, flat_engine._FlatModel)
+    assert list(m.views()) == ["user_emb.weight", "item_emb.weight", "user_bias.weight", "item_bias.weight", "global_bias"]
+    assert m.offset_of("global_bias") == m.flat.numel() - 1
+    positional, named = m._views(m.flat), list(m.views().values())
+    assert len(positional) == len(named) == 5
+    for p, v in zip(positional, named):
+        assert p.data_ptr() == v.data_ptr() and p.shape == v.shape
+    # ... and the base does not depend on this subclass of it
+    assert ".mf import" not in inspect.getsource(flat_engine)
 
 
 def test_index_tensor_normalises_every_id_input():

@@ -308,6 +308,18 @@ def test_out_of_range_index_raises_indexerror(hip_device):
     assert np.isfinite(loss)
     with pytest.raises(IndexError):
         eng.model.predict(np.array([0, 11]), np.array([0, 1]))
+    # a backward_only that raises leaves no gradient behind: the next step is the step of a fresh engine (every row
+    # of `ok` has one contributor, so no float sum depends on order)
+    torch.manual_seed(7)
+    first = make_engine(10, 10, 8, "sgd", "bpr", 0.1, 4)
+    torch.manual_seed(7)
+    fresh = make_engine(10, 10, 8, "sgd", "bpr", 0.1, 4)
+    assert torch.equal(first.model.flat, fresh.model.flat)
+    with pytest.raises(IndexError):
+        first.backward_only((torch.tensor([1, 2]), torch.tensor([3, 10]), torch.tensor([5, 6])))
+    first.train_single_batch(ok)
+    fresh.train_single_batch(ok)
+    assert torch.equal(first.model.flat, fresh.model.flat)
 
 
 def test_batch_of_one_and_bad_loss(hip_device):
