@@ -139,6 +139,12 @@ class UltraGcnParams(Structure):
                 ("negative_weight", c_float), ("gamma", c_float), ("lambda_", c_float)]
 
 
+class SasrecShape(Structure):
+    """hiprec_sasrec_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_items", c_int64), ("dim", c_int32), ("heads", c_int32), ("maxlen", c_int32), ("n_blocks", c_int32)]
+
+
 class T2vTables(Structure):
     """hiprec_t2v_tables (include/hiprec.h)."""
 
@@ -389,6 +395,14 @@ SIGNATURES = {
          c_int32, c_int, c_double, c_double, c_double, c_double, _P, _P, _P, _P, c_int64, _P, c_size_t, _P, _P,
          c_size_t, _P],
     ),
+    "hiprec_sasrec_shape_bytes": (c_size_t, []),
+    "hiprec_sasrec_param_floats": (c_int64, [POINTER(SasrecShape)]),
+    "hiprec_sasrec_workspace_bytes": (c_size_t, [POINTER(SasrecShape), c_int64, c_int32]),
+    "hiprec_sasrec_grad": (
+        c_int,
+        [POINTER(SasrecShape), _P, _P, _P, _P, _P, c_int64, c_int32, c_float, _P, c_float, _P, _P, _P, c_size_t, _P,
+         c_size_t, _P],
+    ),
     "hiprec_alias_sample": (c_int, [_P, _P, _P, c_int64, ctypes.c_uint64, _P, c_int64, _P]),
     "hiprec_ngcf_plan_bytes": (c_size_t, []),
     "hiprec_ngcf_forward": (c_int, [POINTER(NgcfPlan), c_int, _P]),
@@ -572,6 +586,8 @@ def load():
         raise RuntimeError("hiprec_shard_bufs layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_cmn_tables_bytes() != ctypes.sizeof(CmnTables):
         raise RuntimeError("hiprec_cmn_tables layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_sasrec_shape_bytes() != ctypes.sizeof(SasrecShape):
+        raise RuntimeError("hiprec_sasrec_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_ncf_plan_bytes() != ctypes.sizeof(NcfPlan):
         raise RuntimeError("hiprec_ncf_plan layout mismatch between _lib.py and libhiprec.so")
     _lib = _DeviceGuardedLib(lib)

@@ -143,3 +143,54 @@ def instance_mul_neg_loader(data, batch_size, device, num_negative, seed=None):
     neg = sample_negatives(users, items, data.n_users, data.n_items, int(num_negative), seed, dev)
     print(f"Making PairwiseNegativeDataset of length {users.numel()}")
     return DeviceTensorBatcher((users, items, neg), batch_size, shuffle=True)
+
+
+class SequenceSampler:
+    """Host-side batches for SASRec, by the rule of the reference's ``sample_function``
+    (beta_rec/recommenders/sasrec.py:31-77), vectorised in numpy: a uniformly random user with at least two items;
+    ``seq`` the last ``maxlen`` items before the final one, ``pos`` the item that follows each of them, ``neg`` one item
+    per real position drawn uniformly from 1 .. n_items outside the user's set; all three left-padded with 0.
+
+    ``user_train``: dict user id -> list of item ids (1-based, in time order).  ``next_batch()`` returns
+    ``(users [B], seq [B, maxlen], pos [B, maxlen], neg [B, maxlen])`` int64 arrays -- what ``SASRecEngine.
+    train_an_epoch`` asks for.  Same distribution as the reference's sampler, not its RNG stream; the same ``seed`` gives
+    the same batches.  ``n_users`` is kept for the reference's signature."""
+
+    def __init__(self, user_train, n_users, n_items, batch_size, maxlen, seed=0):
+        self.n_users, self.n_items = int(n_users), int(n_items)
+        self.batch_size, self.maxlen = int(batch_size), int(maxlen)
+        self.users = np.array(sorted(u for u, items in user_train.items() if len(items) >= 2), dtype=np.int64)
+        if self.users.size == 0:
+            raise ValueError("no user has two or more items")
+        self.items = {int(u): np.asarray(user_train[u], dtype=np.int64) for u in self.users}
+        for u, items in self.items.items():
+            if items.min() < 1 or items.max() > self.n_items:
+                raise IndexError(f"user {u} holds an item outside [1, {self.n_items}]")
+            if np.unique(items).size >= self.n_items:
+                raise ValueError(f"user {u} has interacted with every item: no negative exists")
+        self.rng = np.random.default_rng(seed)
+
+    def _negatives(self, n, taken):
+        """``n`` ids uniform over 1 .. n_items outside the sorted array ``taken`` (rejection, all at once)."""
+        out = self.rng.integers(1, self.n_items + 1, n)
+        while True:
+            at = np.searchsorted(taken, out)
+            bad = (at < taken.size) & (taken[np.minimum(at, taken.size - 1)] == out)
+            if not bad.any():
+                return out
+            out[bad] = self.rng.integers(1, self.n_items + 1, int(bad.sum()))
+
+    def next_batch(self):
+        B, T = self.batch_size, self.maxlen
+        users = self.users[self.rng.integers(0, self.users.size, B)]
+        seq, pos, neg = (np.zeros((B, T), dtype=np.int64) for _ in range(3))
+        for b, u in enumerate(users):
+            items = self.items[int(u)]
+            n = min(T, items.size - 1)
+            seq[b, T - n:] = items[-n - 1:-1]
+            pos[b, T - n:] = items[-n:]
+            neg[b, T - n:] = self._negatives(n, np.unique(items))
+        return users, seq, pos, neg
+
+    def close(self):
+        """The reference's sampler owns worker processes; this one owns nothing."""

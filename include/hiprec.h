@@ -1427,6 +1427,40 @@ int hiprec_ultragcn_epoch(const hiprec_ultragcn_tables* w, const hiprec_ultragcn
                           float* flat_v, int64_t n_flat, void* sumsq_workspace, size_t sumsq_workspace_bytes,
                           hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ================= SASRec (beta_rec/models/sasrec.py) ==============================================
+ * The parameters live in ONE flat buffer in state_dict() order: item_emb [n_items + 1, dim] (row 0 = padding),
+ * pos_emb [maxlen, dim]; attention_layernorms.{k}.{weight, bias}; attention_layers.{k}.{in_proj_weight [3 dim, dim],
+ * in_proj_bias, out_proj.weight, out_proj.bias}; forward_layernorms.{k}.{weight, bias};
+ * forward_layers.{k}.{conv1.weight [dim, dim, 1], conv1.bias, conv2.weight, conv2.bias}; last_layernorm.{weight, bias},
+ * each group for k = 0 .. n_blocks - 1.  dim <= 128, dim / heads in {16, 32, 64}, maxlen <= 256. */
+typedef struct hiprec_sasrec_shape {
+  int64_t n_items;
+  int32_t dim;
+  int32_t heads;
+  int32_t maxlen;
+  int32_t n_blocks;
+} hiprec_sasrec_shape;
+size_t hiprec_sasrec_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_sasrec_param_floats(const hiprec_sasrec_shape* shape);
+/* bytes of device workspace a hiprec_sasrec_grad call on `batch` sequences of `seq_len` positions needs */
+size_t hiprec_sasrec_workspace_bytes(const hiprec_sasrec_shape* shape, int64_t batch, int32_t seq_len);
+
+/* ---- zero_grad + forward + loss + backward of SASRecEngine.train_single_batch (sasrec.py:205-221) on seq / pos / neg
+ * [batch, seq_len] (ids in [0, n_items], 0 = padding): loss = mean over pos != 0 of BCEWithLogits(<feats, E[pos]>, 1) +
+ * the same of BCEWithLogits(<feats, E[neg]>, 0) + l2_emb * ||item_emb||_2.  Accumulates into the dense gradient g_flat
+ * (zero on entry, laid out like w_flat), leaves the loss partials in scratch and advances the step counter.
+ * keep: NULL (no dropout) or a HOST array of 1 + 3 n_blocks device pointers to keep bytes in the reference's call
+ * order: embedding [batch * seq_len, dim]; per block the attention probabilities [batch * heads, seq_len, seq_len],
+ * dropout1 and dropout2 [batch * seq_len, dim]; a kept value is multiplied by keep_scale.
+ * g_flat == NULL: forward only in eval mode (keep ignored, no loss): feats_out [batch * seq_len, dim] receives
+ * last_layernorm's output; pos / neg / scratch may then be NULL.
+ * An id outside [0, n_items] sets HIPREC_STATUS_ITEM_OOB and its token is skipped. */
+int hiprec_sasrec_grad(const hiprec_sasrec_shape* shape, const float* w_flat, float* g_flat, const int64_t* seq,
+                       const int64_t* pos, const int64_t* neg, int64_t batch, int32_t seq_len, float l2_emb,
+                       const uint8_t* const* keep, float keep_scale, float* feats_out, hiprec_stats* stats,
+                       void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
