@@ -64,6 +64,59 @@ __device__ __forceinline__ TripleIdx load_triple(const hiprec_mf_tables& w,
   return r;
 }
 
+// neg_logsigmoid (common.hpp) in its two halves.  The gradient needs only sigmoid(-x); the loss term is a
+// statistic whose log1pf inlines to ~110 VALU instructions, a quarter of what a gather wave issues per trip.  So
+// each wave of the fused step parks its x = yp - yn in LDS and ONE wave of the block evaluates the block's kAggWaves
+// loss terms, one per lane, behind its own head atomics (mf_bpr_grad_kernel keeps neg_logsigmoid in every wave: with
+// the split its NPL == 4 instantiation passes 64 VGPRs, i.e. one block per CU; profiles/r06_experiments.md 77).  Both halves recompute z from x with neg_logsigmoid's operations in
+// neg_logsigmoid's order: the same bits.
+__device__ __forceinline__ float bpr_sig_neg(float x) {
+  const float z = expf(-fabsf(x));
+  const float frac = z / (1.0f + z);
+  return x < 0.0f ? 1.0f - frac : frac;
+}
+
+// -logsigmoid(x); exactly +0 for x = +inf, which is what a wave without a valid triple parks
+__device__ __forceinline__ float bpr_loss_term(float x) {
+  const float z = expf(-fabsf(x));
+  return log1pf(z) - fminf(x, 0.0f);
+}
+
+constexpr int kLossWave = kAggWaves - 1;  // the wave that evaluates the block's loss terms
+
+// Lanes 0..kAggWaves-1 of wave kLossWave add this trip's loss terms to `loss_lane` (lane i = wave i's running
+// loss, in trip order).  Called right after the trip's second lds_barrier(): s_x is rewritten only behind the
+// next trip's first barrier, which this wave reaches with its LDS reads complete.
+__device__ __forceinline__ void bpr_loss_accumulate(const float* s_x, int wv, int lane, float& loss_lane) {
+  if (wv == kLossWave && lane < kAggWaves) loss_lane += bpr_loss_term(s_x[lane]);
+}
+
+// publish_partials (common.hpp) for a block whose per-wave losses sit in the lanes of wave kLossWave
+__device__ __forceinline__ void bpr_publish_partials(float loss_lane, float reg_lane, float gb_w, float inv_batch,
+                                                     Scratch* scratch, uint32_t n_partials) {
+  __shared__ float s_loss[kAggWaves], s_reg[kAggWaves], s_gbv[kAggWaves];
+  const int lane = lane_id();
+  const int wv = wave_in_block();
+  const float reg_w = wave_sum(reg_lane);
+  if (wv == kLossWave && lane < kAggWaves) s_loss[lane] = loss_lane;
+  if (lane == 0) {
+    s_reg[wv] = reg_w;
+    s_gbv[wv] = gb_w;
+  }
+  lds_barrier();
+  if (threadIdx.x == 0) {
+    float l = 0.f, r = 0.f, b = 0.f;
+#pragma unroll
+    for (int i = 0; i < kAggWaves; ++i) {
+      l += s_loss[i];
+      r += s_reg[i];
+      b += s_gbv[i];
+    }
+    scratch->partials[blockIdx.x] = make_float4(l * inv_batch, r * inv_batch, b, 0.f);
+    if (blockIdx.x == 0) scratch->n_partials = n_partials;
+  }
+}
+
 template <int NPL>
 __global__ __launch_bounds__(kAggBlock) void mf_bpr_grad_kernel(
     hiprec_mf_tables w, hiprec_mf_tables g, const int64_t* __restrict__ users,
@@ -287,6 +340,7 @@ void mf_bpr_fused_kernel(
     hiprec_stats* stats, Scratch* scratch) {
   extern __shared__ __attribute__((aligned(16))) float s_acc[];
   __shared__ long long s_item[kAggWaves];
+  __shared__ float s_x[kAggWaves];  // yp - yn of each wave's triple this trip (+inf: none)
   const int lane = lane_id();
   const int wv = wave_in_block();
   constexpr bool kHasM = KIND == HIPREC_OPT_ADAM;
@@ -408,7 +462,8 @@ void mf_bpr_fused_kernel(
   float gb = 0.f;
   bool gb_ready = false;
 
-  float loss_acc = 0.f, reg_acc = 0.f, gb_acc = 0.f;
+  float loss_lane = 0.f;  // wave kLossWave: lane i = loss of wave i's triples
+  float reg_acc = 0.f, gb_acc = 0.f;
 
   for (int64_t base = static_cast<int64_t>(blockIdx.x) * kAggWaves; base < batch;
        base += static_cast<int64_t>(f.n_gather_blocks) * kAggWaves) {
@@ -437,6 +492,7 @@ void mf_bpr_fused_kernel(
 
     float uu[NPL], pp[NPL];
     float dpos = 0.f, bp = 0.f;
+    float x = __builtin_inff();
     if (valid) {
       const int64_t ou = u * D, op = o_ie + p * D, on = o_ie + n * D;  // rows inside a flat buffer
       float nn[NPL];
@@ -522,9 +578,8 @@ void mf_bpr_fused_kernel(
       }
       const float yp = sigmoid_f32(((dp + bu) + bp) + gb);
       const float yn = sigmoid_f32(((dn + bu) + bn) + gb);
-      float sig_neg_x;
-      const float nls = neg_logsigmoid(yp - yn, &sig_neg_x);
-      const float delta = -sig_neg_x * inv_batch;
+      x = yp - yn;  // its loss term: bpr_loss_accumulate
+      const float delta = -bpr_sig_neg(x) * inv_batch;
       dpos = delta * ((1.f - yp) * yp);
       const float dneg = -delta * ((1.f - yn) * yn);
       float* gur = gf + ou;
@@ -545,9 +600,9 @@ void mf_bpr_fused_kernel(
         slot[D] = dpos + ri * bp;
         reg_acc += 2.f * bu * bu + bp * bp + bn * bn;
       }
-      loss_acc += nls;
       gb_acc += dpos + dneg;
     }
+    if (lane == 0) s_x[wv] = x;  // every trip: a stale value can never be read
     lds_barrier();
     if (valid && is_head) {  // the head sums its run's slots: plain LDS reads instead of LDS float atomics
       float* gpr = gf + o_ie + p * D;
@@ -557,27 +612,10 @@ void mf_bpr_fused_kernel(
         atomic_add_f32(c < D ? gpr + c : gf + o_ib + p, t);
       }
     }
+    bpr_loss_accumulate(s_x, wv, lane, loss_lane);
   }
   // publish this step's partials; n_partials = number of GATHER blocks
-  __shared__ float s_loss[kAggWaves], s_reg[kAggWaves], s_gbv[kAggWaves];
-  const float reg_w = wave_sum(reg_acc);
-  if (lane == 0) {
-    s_loss[wv] = loss_acc;
-    s_reg[wv] = reg_w;
-    s_gbv[wv] = gb_acc;
-  }
-  lds_barrier();
-  if (threadIdx.x == 0) {
-    float l = 0.f, r = 0.f, b = 0.f;
-#pragma unroll
-    for (int i = 0; i < kAggWaves; ++i) {
-      l += s_loss[i];
-      r += s_reg[i];
-      b += s_gbv[i];
-    }
-    scratch->partials[blockIdx.x] = make_float4(l * inv_batch, r * inv_batch, b, 0.f);
-    if (blockIdx.x == 0) scratch->n_partials = static_cast<uint32_t>(f.n_gather_blocks);
-  }
+  bpr_publish_partials(loss_lane, reg_acc, gb_acc, inv_batch, scratch, static_cast<uint32_t>(f.n_gather_blocks));
 }
 
 template <int NPL>
