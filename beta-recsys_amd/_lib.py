@@ -145,6 +145,13 @@ class SasrecShape(Structure):
     _fields_ = [("n_items", c_int64), ("dim", c_int32), ("heads", c_int32), ("maxlen", c_int32), ("n_blocks", c_int32)]
 
 
+class TisasrecShape(Structure):
+    """hiprec_tisasrec_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_items", c_int64), ("dim", c_int32), ("heads", c_int32), ("maxlen", c_int32),
+                ("time_span", c_int32), ("n_blocks", c_int32), ("_pad", c_int32)]
+
+
 class T2vTables(Structure):
     """hiprec_t2v_tables (include/hiprec.h)."""
 
@@ -403,6 +410,15 @@ SIGNATURES = {
         [POINTER(SasrecShape), _P, _P, _P, _P, _P, c_int64, c_int32, c_float, _P, c_float, _P, _P, _P, c_size_t, _P,
          c_size_t, _P],
     ),
+    "hiprec_tisasrec_shape_bytes": (c_size_t, []),
+    "hiprec_tisasrec_param_floats": (c_int64, [POINTER(TisasrecShape)]),
+    "hiprec_tisasrec_workspace_bytes": (c_size_t, [POINTER(TisasrecShape), c_int64, c_int32]),
+    "hiprec_tisasrec_grad": (
+        c_int,
+        [POINTER(TisasrecShape), _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_float, _P, c_float, _P, _P, _P, c_size_t,
+         _P, c_size_t, _P],
+    ),
+    "hiprec_time_relation": (c_int, [_P, c_int64, c_int32, c_int32, _P, _P]),
     "hiprec_alias_sample": (c_int, [_P, _P, _P, c_int64, ctypes.c_uint64, _P, c_int64, _P]),
     "hiprec_ngcf_plan_bytes": (c_size_t, []),
     "hiprec_ngcf_forward": (c_int, [POINTER(NgcfPlan), c_int, _P]),
@@ -588,6 +604,8 @@ def load():
         raise RuntimeError("hiprec_cmn_tables layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_sasrec_shape_bytes() != ctypes.sizeof(SasrecShape):
         raise RuntimeError("hiprec_sasrec_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_tisasrec_shape_bytes() != ctypes.sizeof(TisasrecShape):
+        raise RuntimeError("hiprec_tisasrec_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_ncf_plan_bytes() != ctypes.sizeof(NcfPlan):
         raise RuntimeError("hiprec_ncf_plan layout mismatch between _lib.py and libhiprec.so")
     _lib = _DeviceGuardedLib(lib)

@@ -8,7 +8,7 @@ importing ``beta_rec.recommenders``.
 import sys
 
 # reference module name -> mirror module in this package.  ``beta_rec.models.torch_engine`` is NOT in
-# this table: about fifteen reference engines this package does not mirror (vbcar, narm, tisasrec, sgl,
+# this table: about fifteen reference engines this package does not mirror (vbcar, narm, sgl,
 # vaecf ...) import ``ModelEngine`` from it and need the torch optimizer it builds
 # (``self.optimizer.step()``); the mirrors import their own base class relatively.
 MIRRORS = {
@@ -21,6 +21,7 @@ MIRRORS = {
     "beta_rec.models.pairwise_gmf": "pairwise_gmf",
     "beta_rec.models.cmn": "cmn",
     "beta_rec.models.sasrec": "sasrec",
+    "beta_rec.models.tisasrec": "tisasrec",
     "beta_rec.models.triple2vec": "triple2vec",
     "beta_rec.models.ultragcn": "ultragcn",
 }

@@ -194,3 +194,42 @@ class SequenceSampler:
 
     def close(self):
         """The reference's sampler owns worker processes; this one owns nothing."""
+
+
+def time_relation(time_seq, time_span):
+    """The reference's ``computeRePos`` (beta_rec/recommenders/tisasrec.py:108-127) for one ``[T]`` sequence or a batch
+    ``[B, T]`` of them: ``min(|t_i - t_j|, time_span)`` as int32 ``[..., T, T]``."""
+    ts = np.asarray(time_seq, dtype=np.int64)
+    return np.minimum(np.abs(ts[..., :, None] - ts[..., None, :]), int(time_span)).astype(np.int32)
+
+
+class TimeSequenceSampler(SequenceSampler):
+    """Host-side batches for TiSASRec, by the rule of the reference's ``sample_function``
+    (beta_rec/recommenders/tisasrec.py:220-279), vectorised like :class:`SequenceSampler`: what that class draws, plus
+    ``time_seq`` (the time stamps of ``seq``, 0 at padded positions) and ``time_matrix = time_relation(time_seq,
+    time_span)`` (the reference looks the latter up in a per-user table it builds beforehand by the same rule).
+
+    ``user_train``: dict user id -> list of ``[item, time]`` pairs (items 1-based, integer times, in time order).
+    ``next_batch()`` returns ``(users [B], seq [B, maxlen], time_seq [B, maxlen], time_matrix [B, maxlen, maxlen] int32,
+    pos [B, maxlen], neg [B, maxlen])`` -- what ``TiSASRecEngine.train_an_epoch`` asks for."""
+
+    def __init__(self, user_train, n_users, n_items, batch_size, maxlen, time_span, seed=0):
+        for u, pairs in user_train.items():
+            if any(len(p) != 2 for p in pairs):
+                raise ValueError(f"user {u}: every entry must be an [item, time] pair")
+        super().__init__({u: [p[0] for p in pairs] for u, pairs in user_train.items()}, n_users, n_items, batch_size,
+                         maxlen, seed)
+        self.time_span = int(time_span)
+        if self.time_span < 1:
+            raise ValueError("time_span must be >= 1")
+        self.times = {int(u): np.asarray([p[1] for p in user_train[u]], dtype=np.int64) for u in self.users}
+
+    def next_batch(self):
+        users, seq, pos, neg = super().next_batch()
+        B, T = seq.shape
+        time_seq = np.zeros((B, T), dtype=np.int64)
+        for b, u in enumerate(users):
+            times = self.times[int(u)]
+            n = min(T, times.size - 1)
+            time_seq[b, T - n:] = times[-n - 1:-1]
+        return users, seq, time_seq, time_relation(time_seq, self.time_span), pos, neg

@@ -1461,6 +1461,54 @@ int hiprec_sasrec_grad(const hiprec_sasrec_shape* shape, const float* w_flat, fl
                        const uint8_t* const* keep, float keep_scale, float* feats_out, hiprec_stats* stats,
                        void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ================= TiSASRec (beta_rec/models/tisasrec.py) ==========================================
+ * The parameters live in ONE flat buffer in state_dict() order: item_emb [n_items + 1, dim] (row 0 = padding),
+ * abs_pos_K_emb, abs_pos_V_emb [maxlen, dim], time_matrix_K_emb, time_matrix_V_emb [time_span + 1, dim];
+ * attention_layernorms.{k}.{weight, bias}; attention_layers.{k}.{Q_w, K_w, V_w}.{weight [dim, dim], bias} (no output
+ * projection); forward_layernorms.{k}.{weight, bias}; forward_layers.{k}.{conv1, conv2}.{weight [dim, dim, 1], bias};
+ * last_layernorm.{weight, bias}, each group for k = 0 .. n_blocks - 1.
+ * dim <= 128, dim / heads in {16, 32, 64}, maxlen <= 256, time_span <= 256 (the head's slice of one time table,
+ * (time_span + 1) x 64 fp32 = 66 KB, sits in the 160 KB LDS next to the score rows). */
+typedef struct hiprec_tisasrec_shape {
+  int64_t n_items;
+  int32_t dim;
+  int32_t heads;
+  int32_t maxlen;
+  int32_t time_span;
+  int32_t n_blocks;
+  int32_t _pad;
+} hiprec_tisasrec_shape;
+size_t hiprec_tisasrec_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_tisasrec_param_floats(const hiprec_tisasrec_shape* shape);
+/* bytes of device workspace a hiprec_tisasrec_grad call on `batch` sequences of `seq_len` positions needs (0 for an
+ * unsupported shape).  It holds no [batch, seq_len, seq_len] fp32 buffer of any kind. */
+size_t hiprec_tisasrec_workspace_bytes(const hiprec_tisasrec_shape* shape, int64_t batch, int32_t seq_len);
+
+/* ---- zero_grad + forward + loss + backward of TiSASRecEngine.train_single_batch (tisasrec.py:375-394) on seq / pos /
+ * neg [batch, seq_len] (ids in [0, n_items], 0 = padding) and time_matrix int32 [batch, seq_len, seq_len] (entries in
+ * [0, time_span]; ANY matrix, it need not be symmetric).  The loss is SASRec's.  Accumulates into the dense gradient
+ * g_flat (zero on entry, laid out like w_flat), leaves the loss partials in scratch and advances the step counter.
+ * Every gradient except item_emb's (row atomics) is the same bit for bit from run to run.
+ * keep: NULL (no dropout) or a HOST array of 5 + 3 n_blocks device pointers to keep bytes in the reference's call
+ * order: embedding, abs-pos-K, abs-pos-V [batch * seq_len, dim]; time-K, time-V [batch, seq_len, seq_len, dim] (these
+ * four are shared by every block); then per block the attention probabilities [heads * batch, seq_len, seq_len]
+ * (head-major, as the reference concatenates its heads), dropout1 and dropout2 [batch * seq_len, dim]; a kept value is
+ * multiplied by keep_scale.
+ * g_flat == NULL: forward only in eval mode (no loss): feats_out [batch * seq_len, dim] receives last_layernorm's
+ * output; pos / neg / scratch may then be NULL.
+ * An id outside [0, n_items] sets HIPREC_STATUS_ITEM_OOB and its token is skipped; a time_matrix entry outside
+ * [0, time_span] sets HIPREC_STATUS_ROW_OOB and is clamped, so that nothing is read or written out of range. */
+int hiprec_tisasrec_grad(const hiprec_tisasrec_shape* shape, const float* w_flat, float* g_flat, const int64_t* seq,
+                         const int32_t* time_matrix, const int64_t* pos, const int64_t* neg, int64_t batch,
+                         int32_t seq_len, float l2_emb, const uint8_t* const* keep, float keep_scale, float* feats_out,
+                         hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* out[b, i, j] = min(|time_seq[b, i] - time_seq[b, j]|, time_span): the reference's computeRePos for a whole batch */
+int hiprec_time_relation(const int64_t* time_seq, int64_t batch, int32_t seq_len, int32_t time_span, int32_t* out,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
