@@ -19,74 +19,19 @@
 //             t = g mod (256 / hd) and scans the tile's (i, j) pairs in order.  Per-sequence slabs [B, span + 1, D]
 //             are then summed over b by one thread per element, in order.
 //
-// LayerNorm, the loss stage, the norm prep and the embed are csrc/sasrec.hip's, COPIED here: that file's
-// kernels are not in a header, and moving them would have changed the sources SASRec's evidence is stamped with.
-#include <type_traits>
+// LayerNorm, the loss stage, the norm prep, the embed, the feed-forward GEMM groups and the attention's MFMA / tile
+// helpers are shared with SASRec: csrc/seqrec.hpp, csrc/seqrec.hip.
 #include <vector>
 
-#include "common.hpp"
 #include "gemm.hpp"
+#include "seqrec.hpp"
 
 namespace hiprec {
 namespace {
 
-using tis_f32x4 = __attribute__((ext_vector_type(4))) float;
-
-constexpr int kTisMaxDim = 128;
-constexpr int kTisMaxLen = 256;
 constexpr int kTisMaxSpan = 256;     // (span + 1) x (64 + 1) fp32 = 66.8 KB of the 160 KB LDS
-constexpr int kTisNormParts = 256;
-constexpr int kTisAux = 2 + kTisNormParts;
-constexpr int kTisSLd = kTisMaxLen + 4;   // leading dimension of the score rows in LDS
+constexpr int kTisSLd = kSeqMaxLen + 4;   // leading dimension of the score rows in LDS
 constexpr int kTisFixedKeep = 5;          // embedding, abs-pos-K, abs-pos-V, time-K, time-V
-
-// ---- prep: count(pos != 0) and the first level of sum(W^2) (sasrec.hip) ----------------------------------------------
-__global__ __launch_bounds__(kBlock) void tis_prep_kernel(const float* __restrict__ W, int64_t n_w,
-                                                          const int64_t* __restrict__ pos, int64_t M, int with_norm,
-                                                          float* __restrict__ aux) {
-  __shared__ float s_red[kBlock];
-  float s = 0.f;
-  if (with_norm) {
-    const int64_t per = (n_w + kTisNormParts - 1) / kTisNormParts;
-    const int64_t lo = per * blockIdx.x, hi = min(n_w, lo + per);
-    for (int64_t i = lo + threadIdx.x; i < hi; i += kBlock) s += W[i] * W[i];
-  }
-  s_red[threadIdx.x] = s;
-  __syncthreads();
-  for (int r = kBlock / 2; r > 0; r >>= 1) {
-    if (static_cast<int>(threadIdx.x) < r) s_red[threadIdx.x] += s_red[threadIdx.x + r];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) aux[2 + blockIdx.x] = s_red[0];
-  if (blockIdx.x != 0) return;
-  __syncthreads();
-  float c = 0.f;
-  for (int64_t m = threadIdx.x; m < M; m += kBlock) c += pos[m] != 0 ? 1.f : 0.f;
-  s_red[threadIdx.x] = c;
-  __syncthreads();
-  for (int r = kBlock / 2; r > 0; r >>= 1) {
-    if (static_cast<int>(threadIdx.x) < r) s_red[threadIdx.x] += s_red[threadIdx.x + r];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) aux[0] = s_red[0];
-}
-
-__global__ __launch_bounds__(kBlock) void tis_norm_grad_kernel(const float* __restrict__ W, float* __restrict__ g,
-                                                               int64_t n_w, float l2, float* __restrict__ aux) {
-  __shared__ float s_red[kBlock];
-  s_red[threadIdx.x] = aux[2 + threadIdx.x];
-  __syncthreads();
-  for (int r = kBlock / 2; r > 0; r >>= 1) {
-    if (static_cast<int>(threadIdx.x) < r) s_red[threadIdx.x] += s_red[threadIdx.x + r];
-    __syncthreads();
-  }
-  const float norm = sqrtf(s_red[0]);
-  const float coef = norm > 0.f ? l2 / norm : 0.f;
-  if (blockIdx.x == 0 && threadIdx.x == 0) aux[1] = norm;
-  if (g == nullptr) return;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n_w; i += stride) g[i] += coef * W[i];
-}
 
 // ---- time matrix ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void tis_check_tm_kernel(const int32_t* __restrict__ tm, int64_t n, int span,
@@ -116,27 +61,7 @@ __global__ __launch_bounds__(kBlock) void tis_time_relation_kernel(const int64_t
   }
 }
 
-// ---- embed: x0 = E[seq] * sqrt(D) * keep * (seq != 0), no positional row ----------------------------------------------
-__global__ __launch_bounds__(kBlock) void tis_embed_kernel(const float* __restrict__ E, const int64_t* __restrict__ seq,
-                                                           int64_t M, int D, int64_t n_items, float sqrt_d,
-                                                           const uint8_t* __restrict__ keep, float ks,
-                                                           float* __restrict__ x, hiprec_stats* stats) {
-  const int64_t n = M * D, stride = static_cast<int64_t>(gridDim.x) * kBlock;
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
-    const int64_t m = i / D;
-    const int d = static_cast<int>(i - m * D);
-    const int64_t id = seq[m];
-    float v = 0.f;
-    if (id < 0 || id > n_items) {
-      if (d == 0) atomicOr(&stats->status, HIPREC_STATUS_ITEM_OOB);
-    } else if (id != 0) {
-      v = E[id * D + d] * sqrt_d;
-      if (keep) v = keep[i] ? v * ks : 0.f;
-    }
-    x[i] = v;
-  }
-}
-
+// d item_emb[seq] += dx * keep * sqrt(D) (row atomics, id 0 skipped); there is no positional row to differentiate
 __global__ __launch_bounds__(kBlock) void tis_embed_bwd_kernel(const float* __restrict__ dx,
                                                                const int64_t* __restrict__ seq, int64_t M, int D,
                                                                int64_t n_items, float sqrt_d,
@@ -208,113 +133,7 @@ __global__ __launch_bounds__(kBlock) void tis_table_reduce_kernel(const float* _
   g_v[e] += av;
 }
 
-// ---- LayerNorm (sasrec.hip; the backward takes a second extra gradient: K and V have separate dgrad GEMMs) -----------
-__global__ __launch_bounds__(kBlock) void tis_ln_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                            const int64_t* __restrict__ seq, float* __restrict__ xsum,
-                                                            const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, float* __restrict__ y,
-                                                            float* __restrict__ mean, float* __restrict__ rstd,
-                                                            int64_t M, int D) {
-  const int lane = lane_id();
-  const float inv_d = 1.f / static_cast<float>(D);
-  for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block(); row < M;
-       row += static_cast<int64_t>(gridDim.x) * kWavesPerBlock) {
-    const bool live = !seq || seq[row] != 0;
-    float v[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int d = lane + 64 * h;
-      float t = 0.f;
-      if (d < D && live) {
-        t = a[row * D + d];
-        if (b) t += b[row * D + d];
-      }
-      v[h] = t;
-      if (xsum && d < D) xsum[row * D + d] = t;
-    }
-    const float mu = wave_sum(v[0] + v[1]) * inv_d;
-    const float c0 = lane < D ? v[0] - mu : 0.f, c1 = lane + 64 < D ? v[1] - mu : 0.f;
-    const float var = wave_sum(c0 * c0 + c1 * c1) * inv_d;
-    const float r = 1.0f / sqrtf(var + 1e-8f);
-    if (lane < D) y[row * D + lane] = c0 * r * gamma[lane] + beta[lane];
-    if (lane + 64 < D) y[row * D + lane + 64] = c1 * r * gamma[lane + 64] + beta[lane + 64];
-    if (lane == 0) {
-      mean[row] = mu;
-      rstd[row] = r;
-    }
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void tis_ln_bwd_kernel(
-    const float* __restrict__ dy_a, const float* __restrict__ dy_b, const float* __restrict__ a,
-    const float* __restrict__ b, const float* __restrict__ gamma, const float* __restrict__ mean,
-    const float* __restrict__ rstd, const float* __restrict__ dx_extra, const float* __restrict__ dx_extra2,
-    const int64_t* __restrict__ seq, const uint8_t* __restrict__ keep, float ks, float* __restrict__ dx,
-    float* __restrict__ dx_keep, float* __restrict__ dyx, float* __restrict__ dyt, int64_t M, int D) {
-  const int lane = lane_id();
-  const float inv_d = 1.f / static_cast<float>(D);
-  for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block(); row < M;
-       row += static_cast<int64_t>(gridDim.x) * kWavesPerBlock) {
-    const bool live = !seq || seq[row] != 0;
-    const float mu = mean[row], r = rstd[row];
-    float xh[2], gg[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int d = lane + 64 * h;
-      xh[h] = 0.f;
-      gg[h] = 0.f;
-      if (d < D) {
-        const int64_t i = row * D + d;
-        float x = a[i];
-        if (b) x += b[i];
-        float dy = dy_a[i];
-        if (dy_b) dy += dy_b[i];
-        xh[h] = (x - mu) * r;
-        gg[h] = dy * gamma[d];
-        dyx[i] = dy * xh[h];
-        if (dyt) dyt[i] = dy;
-      }
-    }
-    const float m1 = wave_sum(gg[0] + gg[1]) * inv_d;
-    const float m2 = wave_sum(gg[0] * xh[0] + gg[1] * xh[1]) * inv_d;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int d = lane + 64 * h;
-      if (d < D) {
-        const int64_t i = row * D + d;
-        float v = r * (gg[h] - m1 - xh[h] * m2);
-        if (dx_extra) v += dx_extra[i];
-        if (dx_extra2) v += dx_extra2[i];
-        if (!live) v = 0.f;
-        dx[i] = v;
-        if (dx_keep) dx_keep[i] = keep[i] ? v * ks : 0.f;
-      }
-    }
-  }
-}
-
 // ---- time-interval-aware causal attention ------------------------------------------------------------------------------
-// v_mfma_f32_16x16x4_f32 on operands in LDS (sasrec.hip): element (i, k) of A at A[i * sai + k * sak], element (k, j)
-// of B at B[k * sbk + j * sbj]; the result has col = lane & 15, row = 4 * (lane >> 4) + reg.
-__device__ __forceinline__ tis_f32x4 tis_mma16(tis_f32x4 acc, const float* A, int sai, int sak, const float* B, int sbk,
-                                               int sbj, int K) {
-  const int l = lane_id();
-  const float* ap = A + (l & 15) * sai + (l >> 4) * sak;
-  const float* bp = B + (l >> 4) * sbk + (l & 15) * sbj;
-  for (int k = 0; k < K; k += 4) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[k * sak], bp[k * sbk], acc, 0, 0, 0);
-  return acc;
-}
-
-// rows [r0, r0 + rows) x HD columns of src (leading dimension ld) into dst[rows][HD + 1]; rows >= limit are 0
-template <int HD>
-__device__ __forceinline__ void tis_load_tile(float* dst, const float* __restrict__ src, int64_t ld, int r0, int rows,
-                                              int limit, float scale) {
-  for (int e = threadIdx.x; e < rows * HD; e += kBlock) {
-    const int r = e / HD, c = e - r * HD;
-    dst[r * (HD + 1) + c] = (r0 + r < limit) ? src[static_cast<int64_t>(r0 + r) * ld + c] * scale : 0.f;
-  }
-}
-
 // the head's slice of a [span + 1, D] table into tab[span + 1][HD + 1]
 template <int HD>
 __device__ __forceinline__ void tis_load_table(float* tab, const float* __restrict__ E, int D, int h, int span) {
@@ -322,12 +141,6 @@ __device__ __forceinline__ void tis_load_table(float* tab, const float* __restri
     const int r = e / HD, c = e - r * HD;
     tab[r * (HD + 1) + c] = E[static_cast<int64_t>(r) * D + h * HD + c];
   }
-}
-
-__device__ __forceinline__ float tis_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
 }
 
 // sum_c a[c] * row[c] over the head's HD columns, through HD keep bytes (16-byte aligned) when kp != NULL
@@ -369,7 +182,7 @@ static size_t tis_bwd_lds(int hd, int span) {
   const int qt = hd == 64 ? 16 : 32;
   return sizeof(float) * (static_cast<size_t>(2 * qt + 64) * (hd + 1) + 2 * static_cast<size_t>(qt) * kTisSLd +
                           static_cast<size_t>(span + 1) * (hd + 1) + 3 * qt) +
-         sizeof(uint16_t) * static_cast<size_t>(qt) * kTisMaxLen;
+         sizeof(uint16_t) * static_cast<size_t>(qt) * kSeqMaxLen;
 }
 
 // grid (B * H, ceil(T / QT)).  qkv [M, 3D]: q | k' | v'.  keep_a [H * B, T, T] (the reference's head-major layout),
@@ -394,7 +207,7 @@ __global__ __launch_bounds__(kBlock) void tis_attn_fwd_kernel(
   const int64_t* seq_b = seq + static_cast<int64_t>(b) * T;
   const int32_t* tm_b = tm + static_cast<int64_t>(b) * T * T;
   const float scale = 1.0f / sqrtf(static_cast<float>(HD));
-  tis_load_tile<HD>(Qs, base, ld, q0, QT, T, scale);
+  load_tile<HD>(Qs, base, ld, q0, QT, T, scale);
   tis_load_table<HD>(tab, EK, D, h, span);
   const int n_keys = min(T, q0 + QT);
   const int n_chunks = (n_keys + 63) / 64;
@@ -402,13 +215,13 @@ __global__ __launch_bounds__(kBlock) void tis_attn_fwd_kernel(
   for (int ch = 0; ch < n_chunks; ++ch) {
     const int j0 = ch * 64;
     __syncthreads();
-    tis_load_tile<HD>(Ks, base + D, ld, j0, 64, n_keys, 1.f);
+    load_tile<HD>(Ks, base + D, ld, j0, 64, n_keys, 1.f);
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < TisTile<HD>::kRowTiles; ++u) {
       const int tile = wave * TisTile<HD>::kRowTiles + u, rt = tile >> 2, ct = tile & 3;
-      tis_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      acc = tis_mma16(acc, Qs + rt * 16 * LD, LD, 1, Ks + ct * 16 * LD, 1, LD, HD);
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      acc = mma16(acc, Qs + rt * 16 * LD, LD, 1, Ks + ct * 16 * LD, 1, LD, HD);
 #pragma unroll
       for (int r = 0; r < 4; ++r) S[(rt * 16 + 4 * (lane >> 4) + r) * kTisSLd + j0 + ct * 16 + (lane & 15)] = acc[r];
     }
@@ -434,7 +247,7 @@ __global__ __launch_bounds__(kBlock) void tis_attn_fwd_kernel(
     }
     float mx = -INFINITY;
     for (int j = lane; j <= i; j += 64) mx = fmaxf(mx, Sr[j]);
-    mx = tis_wave_max(mx);
+    mx = wave_max(mx);
     float sum = 0.f;
     for (int j = lane; j <= i; j += 64) {
       const float ex = expf(Sr[j] - mx);
@@ -458,13 +271,13 @@ __global__ __launch_bounds__(kBlock) void tis_attn_fwd_kernel(
   tis_load_table<HD>(tab, EV, D, h, span);
   constexpr int kTiles = TisTile<HD>::kRowTiles * TisTile<HD>::kColTiles;    // <= 4: one per wave
   const int rt = wave / TisTile<HD>::kColTiles, ct = wave - rt * TisTile<HD>::kColTiles;
-  tis_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int ch = 0; ch < n_chunks; ++ch) {
     const int j0 = ch * 64;
     __syncthreads();
-    tis_load_tile<HD>(Ks, base + 2 * D, ld, j0, 64, n_keys, 1.f);
+    load_tile<HD>(Ks, base + 2 * D, ld, j0, 64, n_keys, 1.f);
     __syncthreads();
-    if (wave < kTiles) acc = tis_mma16(acc, S + rt * 16 * kTisSLd + j0, kTisSLd, 1, Ks + ct * 16, LD, 1, 64);
+    if (wave < kTiles) acc = mma16(acc, S + rt * 16 * kTisSLd + j0, kTisSLd, 1, Ks + ct * 16, LD, 1, 64);
   }
   // + sum_j P[i, j] drop(EV[tm[i, j]]): lane = column, the rows over the 256 / HD groups, j in order
   {
@@ -516,7 +329,7 @@ __global__ __launch_bounds__(kBlock) void tis_attn_bwd_kernel(
   float* s_lse = tab + (span + 1) * LD;    // [QT]
   float* s_delta = s_lse + QT;             // [QT]
   float* s_live = s_delta + QT;            // [QT] 1 = a real query row of the sequence
-  uint16_t* tms = reinterpret_cast<uint16_t*>(s_live + QT);   // [QT][kTisMaxLen] table rows of the tile's pairs
+  uint16_t* tms = reinterpret_cast<uint16_t*>(s_live + QT);   // [QT][kSeqMaxLen] table rows of the tile's pairs
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
   const int q0 = tile * QT;
   const int lane = lane_id(), wave = wave_in_block();
@@ -530,12 +343,12 @@ __global__ __launch_bounds__(kBlock) void tis_attn_bwd_kernel(
   const int n_keys = min(T, q0 + QT);
   const int n_chunks = (n_keys + 63) / 64;
   const int width = n_chunks * 64;
-  tis_load_tile<HD>(Qs, base, ld, q0, QT, T, scale);
-  tis_load_tile<HD>(Gs, g_base, D, q0, QT, T, 1.f);
+  load_tile<HD>(Qs, base, ld, q0, QT, T, scale);
+  load_tile<HD>(Gs, g_base, D, q0, QT, T, 1.f);
   tis_load_table<HD>(tab, EV, D, h, span);
   for (int e = threadIdx.x; e < QT * n_keys; e += kBlock) {
     const int r = e / n_keys, j = e - r * n_keys, i = q0 + r;
-    tms[r * kTisMaxLen + j] = i < T ? static_cast<uint16_t>(tis_row(tm_b[static_cast<int64_t>(i) * T + j], span)) : 0;
+    tms[r * kSeqMaxLen + j] = i < T ? static_cast<uint16_t>(tis_row(tm_b[static_cast<int64_t>(i) * T + j], span)) : 0;
   }
   __syncthreads();
   if (threadIdx.x < QT * 8) {                 // delta = rowsum(dO * O), 8 threads per row
@@ -557,13 +370,13 @@ __global__ __launch_bounds__(kBlock) void tis_attn_bwd_kernel(
   for (int ch = 0; ch < n_chunks; ++ch) {
     const int j0 = ch * 64;
     __syncthreads();
-    tis_load_tile<HD>(Ks, base + 2 * D, ld, j0, 64, n_keys, 1.f);
+    load_tile<HD>(Ks, base + 2 * D, ld, j0, 64, n_keys, 1.f);
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < TisTile<HD>::kRowTiles; ++u) {
       const int tl = wave * TisTile<HD>::kRowTiles + u, rt = tl >> 2, ct = tl & 3;
-      tis_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      acc = tis_mma16(acc, Gs + rt * 16 * LD, LD, 1, Ks + ct * 16 * LD, 1, LD, HD);
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      acc = mma16(acc, Gs + rt * 16 * LD, LD, 1, Ks + ct * 16 * LD, 1, LD, HD);
 #pragma unroll
       for (int r = 0; r < 4; ++r) DS[(rt * 16 + 4 * (lane >> 4) + r) * kTisSLd + j0 + ct * 16 + (lane & 15)] = acc[r];
     }
@@ -574,7 +387,7 @@ __global__ __launch_bounds__(kBlock) void tis_attn_bwd_kernel(
     if (j > i || s_live[r] == 0.f) continue;
     const uint8_t* kp =
         keep_tv ? keep_tv + ((static_cast<int64_t>(b) * T + i) * T + j) * D + h * HD : nullptr;
-    DS[r * kTisSLd + j] += tis_dot<HD>(Gs + r * LD, tab + tms[r * kTisMaxLen + j] * LD, kp, ks);
+    DS[r * kTisSLd + j] += tis_dot<HD>(Gs + r * LD, tab + tms[r * kSeqMaxLen + j] * LD, kp, ks);
   }
   __syncthreads();
   // pass 2 (EK resident): S, P = exp(S - lse), dS = P * (dP through the keep bytes - delta)
@@ -582,13 +395,13 @@ __global__ __launch_bounds__(kBlock) void tis_attn_bwd_kernel(
   for (int ch = 0; ch < n_chunks; ++ch) {
     const int j0 = ch * 64;
     __syncthreads();
-    tis_load_tile<HD>(Ks, base + D, ld, j0, 64, n_keys, 1.f);
+    load_tile<HD>(Ks, base + D, ld, j0, 64, n_keys, 1.f);
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < TisTile<HD>::kRowTiles; ++u) {
       const int tl = wave * TisTile<HD>::kRowTiles + u, rt = tl >> 2, ct = tl & 3;
-      tis_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      acc = tis_mma16(acc, Qs + rt * 16 * LD, LD, 1, Ks + ct * 16 * LD, 1, LD, HD);
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      acc = mma16(acc, Qs + rt * 16 * LD, LD, 1, Ks + ct * 16 * LD, 1, LD, HD);
 #pragma unroll
       for (int r = 0; r < 4; ++r) PD[(rt * 16 + 4 * (lane >> 4) + r) * kTisSLd + j0 + ct * 16 + (lane & 15)] = acc[r];
     }
@@ -600,7 +413,7 @@ __global__ __launch_bounds__(kBlock) void tis_attn_bwd_kernel(
     if (j <= i && s_live[r] != 0.f) {
       const uint8_t* kp =
           keep_tk ? keep_tk + ((static_cast<int64_t>(b) * T + i) * T + j) * D + h * HD : nullptr;
-      const float s = PD[r * kTisSLd + j] + tis_dot<HD>(Qs + r * LD, tab + tms[r * kTisMaxLen + j] * LD, kp, ks);
+      const float s = PD[r * kTisSLd + j] + tis_dot<HD>(Qs + r * LD, tab + tms[r * kSeqMaxLen + j] * LD, kp, ks);
       const float p = expf(s - s_lse[r]);
       float d = DS[r * kTisSLd + j];
       pd = p;
@@ -617,18 +430,18 @@ __global__ __launch_bounds__(kBlock) void tis_attn_bwd_kernel(
   // pass 3: dQ = dS (K' + drop(EK[tm])) / sqrt(hd); this tile's dK' = dS^T q / sqrt(hd) and dV' = P^T dO
   constexpr int kTiles = TisTile<HD>::kRowTiles * TisTile<HD>::kColTiles;    // <= 4: one per wave
   const int qrt = wave / TisTile<HD>::kColTiles, qct = wave - qrt * TisTile<HD>::kColTiles;
-  tis_f32x4 acc_q = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc_q = {0.f, 0.f, 0.f, 0.f};
   for (int ch = 0; ch < n_chunks; ++ch) {
     const int j0 = ch * 64;
     __syncthreads();
-    tis_load_tile<HD>(Ks, base + D, ld, j0, 64, n_keys, 1.f);
+    load_tile<HD>(Ks, base + D, ld, j0, 64, n_keys, 1.f);
     __syncthreads();
-    if (wave < kTiles) acc_q = tis_mma16(acc_q, DS + qrt * 16 * kTisSLd + j0, kTisSLd, 1, Ks + qct * 16, LD, 1, 64);
+    if (wave < kTiles) acc_q = mma16(acc_q, DS + qrt * 16 * kTisSLd + j0, kTisSLd, 1, Ks + qct * 16, LD, 1, 64);
     for (int tl = wave; tl < 4 * TisTile<HD>::kColTiles; tl += kWavesPerBlock) {
       const int jt = tl / TisTile<HD>::kColTiles, ct = tl - jt * TisTile<HD>::kColTiles;
-      tis_f32x4 ak = {0.f, 0.f, 0.f, 0.f}, av = {0.f, 0.f, 0.f, 0.f};
-      ak = tis_mma16(ak, DS + j0 + jt * 16, 1, kTisSLd, Qs + ct * 16, LD, 1, QT);
-      av = tis_mma16(av, PD + j0 + jt * 16, 1, kTisSLd, Gs + ct * 16, LD, 1, QT);
+      f32x4 ak = {0.f, 0.f, 0.f, 0.f}, av = {0.f, 0.f, 0.f, 0.f};
+      ak = mma16(ak, DS + j0 + jt * 16, 1, kTisSLd, Qs + ct * 16, LD, 1, QT);
+      av = mma16(av, PD + j0 + jt * 16, 1, kTisSLd, Gs + ct * 16, LD, 1, QT);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int j = j0 + jt * 16 + 4 * (lane >> 4) + r;
@@ -654,7 +467,7 @@ __global__ __launch_bounds__(kBlock) void tis_attn_bwd_kernel(
       if (s_live[r] != 0.f) {
         const uint8_t* kp = keep_tk ? keep_tk + (static_cast<int64_t>(b) * T + i) * T * D + h * HD + c : nullptr;
         for (int j = 0; j <= i; ++j) {
-          float v = tab[tms[r * kTisMaxLen + j] * LD + c];
+          float v = tab[tms[r * kSeqMaxLen + j] * LD + c];
           if (kp) v = kp[static_cast<int64_t>(j) * D] ? v * ks : 0.f;
           o += DS[r * kTisSLd + j] * v;
         }
@@ -690,7 +503,7 @@ __global__ __launch_bounds__(kBlock) void tis_attn_bwd_kernel(
       const float vr = vec[r * LD + c];
       const uint8_t* kp = keep_t ? keep_t + (static_cast<int64_t>(b) * T + i) * T * D + h * HD + c : nullptr;
       for (int j = 0; j <= i; ++j) {
-        const int t = tms[r * kTisMaxLen + j];
+        const int t = tms[r * kSeqMaxLen + j];
         if ((t & (G - 1)) != g) continue;
         float v = coef[r * kTisSLd + j] * vr;
         if (kp) v = kp[static_cast<int64_t>(j) * D] ? v * ks : 0.f;
@@ -702,67 +515,6 @@ __global__ __launch_bounds__(kBlock) void tis_attn_bwd_kernel(
       const int r = e / HD, cc = e - r * HD;
       slab[static_cast<int64_t>(r) * D + cc] = tab[r * LD + cc];
     }
-  }
-}
-
-// ---- loss: BCE-with-logits over the tokens with pos != 0, d feats, row atomics into d item_emb (sasrec.hip) ----------
-__global__ __launch_bounds__(kBlock) void tis_loss_kernel(const float* __restrict__ feats, const float* __restrict__ E,
-                                                          const int64_t* __restrict__ pos,
-                                                          const int64_t* __restrict__ neg, int64_t M, int D,
-                                                          int64_t n_items, const float* __restrict__ aux, float l2,
-                                                          float* __restrict__ dfeats, float* __restrict__ g_item,
-                                                          Scratch* scratch, hiprec_stats* stats) {
-  __shared__ float s_loss[kWavesPerBlock];
-  const int lane = lane_id(), wave = wave_in_block();
-  const float inv = 1.0f / aux[0];
-  float loss = 0.f;
-  for (int64_t m = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave; m < M;
-       m += static_cast<int64_t>(gridDim.x) * kWavesPerBlock) {
-    const int64_t p = pos[m], n = neg[m];
-    const bool ok = p >= 0 && p <= n_items && n >= 0 && n <= n_items;
-    if (!ok && lane == 0) atomicOr(&stats->status, HIPREC_STATUS_ITEM_OOB);
-    if (!ok || p == 0) {
-      if (lane < D) dfeats[m * D + lane] = 0.f;
-      if (lane + 64 < D) dfeats[m * D + lane + 64] = 0.f;
-      continue;
-    }
-    float f[2], ep[2], en[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int d = lane + 64 * h;
-      f[h] = d < D ? feats[m * D + d] : 0.f;
-      ep[h] = d < D ? E[p * D + d] : 0.f;
-      en[h] = d < D ? E[n * D + d] : 0.f;
-    }
-    const float pl = wave_sum(f[0] * ep[0] + f[1] * ep[1]);
-    const float nl = wave_sum(f[0] * en[0] + f[1] * en[1]);
-    float sig_neg_pl, sig_nl;
-    loss += neg_logsigmoid(pl, &sig_neg_pl);
-    loss += neg_logsigmoid(-nl, &sig_nl);
-    const float dpl = -sig_neg_pl * inv, dnl = sig_nl * inv;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int d = lane + 64 * h;
-      if (d < D) {
-        dfeats[m * D + d] = dpl * ep[h] + dnl * en[h];
-        atomic_add_f32(g_item + p * D + d, dpl * f[h]);
-        if (n != 0) atomic_add_f32(g_item + n * D + d, dnl * f[h]);
-      }
-    }
-  }
-  if (lane == 0) s_loss[wave] = loss;
-  lds_barrier();
-  if (threadIdx.x == 0) {
-    float l = 0.f;
-#pragma unroll
-    for (int i = 0; i < kWavesPerBlock; ++i) l += s_loss[i];
-    l *= inv;
-    if (blockIdx.x == 0) {
-      if (l2 != 0.f) l += l2 * aux[1];
-      scratch->n_partials = gridDim.x;
-      advance_step(stats);
-    }
-    scratch->partials[blockIdx.x] = make_float4(l, 0.f, 0.f, 0.f);
   }
 }
 
@@ -825,7 +577,7 @@ static TisWorkspace tis_carve(float* base, const hiprec_tisasrec_shape& s, int64
   w.x_last = take(MD); w.feats = take(MD); w.mean_l = take(M); w.rstd_l = take(M); w.z = take(MD);
   for (int i = 0; i < 8; ++i) w.t[i] = take(MD);
   w.dqkv = take(3 * MD);
-  w.aux = take(kTisAux);
+  w.aux = take(kSeqAux);
   w.cs_each = colsum_ws_floats(static_cast<int>(M), s.dim);
   w.cs = take(3 * w.cs_each);
   w.slab_floats = B * static_cast<int64_t>(s.time_span + 1) * s.dim;     // one [span + 1, D] slab per sequence
@@ -837,46 +589,10 @@ static TisWorkspace tis_carve(float* base, const hiprec_tisasrec_shape& s, int64
 
 static int tis_check_shape(const hiprec_tisasrec_shape* s) {
   HIPREC_REQUIRE(s, "NULL shape");
-  HIPREC_REQUIRE(s->n_items > 0 && s->n_blocks >= 1 && s->heads >= 1 && s->maxlen >= 1 && s->time_span >= 1,
-                 "bad TiSASRec shape");
-  HIPREC_REQUIRE(s->dim <= kTisMaxDim && s->dim % s->heads == 0,
-                 "TiSASRec needs emb_dim <= %d and a multiple of num_heads", kTisMaxDim);
-  const int hd = s->dim / s->heads;
-  HIPREC_REQUIRE(hd == 16 || hd == 32 || hd == 64, "TiSASRec needs a head width of 16, 32 or 64 (got %d)", hd);
-  HIPREC_REQUIRE(s->maxlen <= kTisMaxLen, "TiSASRec needs maxlen <= %d (got %d)", kTisMaxLen, s->maxlen);
+  if (int rc = seq_check_shape("TiSASRec", s->n_items, s->n_blocks, s->heads, s->maxlen, s->dim)) return rc;
+  HIPREC_REQUIRE(s->time_span >= 1, "bad TiSASRec shape");
   HIPREC_REQUIRE(s->time_span <= kTisMaxSpan, "TiSASRec needs time_span <= %d (got %d)", kTisMaxSpan, s->time_span);
   return 0;
-}
-
-static int tis_ln_fwd(const float* a, const float* b, const int64_t* seq, float* xsum, const float* gamma,
-                      const float* beta, float* y, float* mean, float* rstd, int64_t M, int D, hipStream_t st) {
-  tis_ln_fwd_kernel<<<grid_for_waves(M), kBlock, 0, st>>>(a, b, seq, xsum, gamma, beta, y, mean, rstd, M, D);
-  HIPREC_TRY(hipGetLastError());
-  return 0;
-}
-
-static int tis_ln_bwd(const float* dy_a, const float* dy_b, const float* a, const float* b, const float* gamma,
-                      const float* mean, const float* rstd, const float* dx_extra, const float* dx_extra2,
-                      const int64_t* seq, const uint8_t* keep, float ks, float* dx, float* dx_keep, float* dyx,
-                      float* dyt, float* g_gamma, float* g_beta, float* cs, int64_t cs_each, int64_t M, int D,
-                      hipStream_t st) {
-  tis_ln_bwd_kernel<<<grid_for_waves(M), kBlock, 0, st>>>(dy_a, dy_b, a, b, gamma, mean, rstd, dx_extra, dx_extra2, seq,
-                                                           keep, ks, dx, keep ? dx_keep : nullptr, dyx,
-                                                           dy_b ? dyt : nullptr, M, D);
-  HIPREC_TRY(hipGetLastError());
-  GemmGroup g{};
-  g.n = 2;
-  g.p[0] = make_colsum(dyx, static_cast<int>(M), D, D, g_gamma, cs);
-  g.p[1] = make_colsum(dy_b ? dyt : dy_a, static_cast<int>(M), D, D, g_beta, cs + cs_each);
-  if (int rc = launch_group(g, st)) return rc;
-  return launch_colsum_reduce(g, st);
-}
-
-template <typename F>
-static int tis_by_head_width(int hd, F&& f) {
-  if (hd == 16) return f(std::integral_constant<int, 16>{});
-  if (hd == 32) return f(std::integral_constant<int, 32>{});
-  return f(std::integral_constant<int, 64>{});
 }
 
 static std::atomic<uint64_t> g_tis_lds_done[3][2];      // [head width][forward / backward], a bit per device
@@ -907,18 +623,10 @@ static int tis_run(const hiprec_tisasrec_shape& s, float* w_flat, float* g_flat,
 
   tis_check_tm_kernel<<<grid_for_threads(M * T), kBlock, 0, st>>>(tm, M * T, span, stats);
   HIPREC_TRY(hipGetLastError());
-  if (train) {
-    tis_prep_kernel<<<kTisNormParts, kBlock, 0, st>>>(w.item_emb, n_table, pos, M, l2 != 0.f, a.aux);
-    HIPREC_TRY(hipGetLastError());
-    if (l2 != 0.f) {
-      tis_norm_grad_kernel<<<grid_for_threads(n_table), kBlock, 0, st>>>(w.item_emb, g_flat, n_table, l2, a.aux);
-      HIPREC_TRY(hipGetLastError());
-    }
-  }
-  tis_embed_kernel<<<grid_for_threads(M * D), kBlock, 0, st>>>(w.item_emb, seq, M, D, s.n_items, sqrt_d, kp(0), ks,
-                                                               a.x[0], stats);
-  HIPREC_TRY(hipGetLastError());
-  if (int rc = tis_ln_fwd(a.x[0], nullptr, nullptr, nullptr, w.ln_a_w[0], w.ln_a_b[0], a.qn[0], a.mean_a[0],
+  if (train)
+    if (int rc = seq_prep(w.item_emb, g_flat, n_table, pos, M, l2, a.aux, st)) return rc;
+  if (int rc = seq_embed(w.item_emb, nullptr, seq, M, T, D, s.n_items, sqrt_d, kp(0), ks, a.x[0], stats, st)) return rc;
+  if (int rc = seq_ln_fwd(a.x[0], nullptr, nullptr, nullptr, w.ln_a_w[0], w.ln_a_b[0], a.qn[0], a.mean_a[0],
                           a.rstd_a[0], M, D, st))
     return rc;
   for (int k = 0; k < nb; ++k) {
@@ -935,7 +643,7 @@ static int tis_run(const hiprec_tisasrec_shape& s, float* w_flat, float* g_flat,
     tis_pos_fwd_kernel<<<grid_for_threads(M * D), kBlock, 0, st>>>(a.qkv[k], w.pos_k, w.pos_v, M, T, D, kp(1), kp(2),
                                                                    ks);
     HIPREC_TRY(hipGetLastError());
-    if (int rc = tis_by_head_width(hd, [&](auto hwc) {
+    if (int rc = by_head_width(hd, [&](auto hwc) {
           constexpr int HD = decltype(hwc)::value;
           if (int rc2 = tis_allow_lds(reinterpret_cast<const void*>(&tis_attn_fwd_kernel<HD>), HD, hw, 0))
             return rc2;
@@ -945,25 +653,14 @@ static int tis_run(const hiprec_tisasrec_shape& s, float* w_flat, float* g_flat,
           return 0;
         }))
       return rc;
-    if (int rc = tis_ln_fwd(a.qn[k], a.o[k], nullptr, nullptr, w.ln_f_w[k], w.ln_f_b[k], a.f[k], a.mean_f[k],
+    if (int rc = seq_ln_fwd(a.qn[k], a.o[k], nullptr, nullptr, w.ln_f_w[k], w.ln_f_b[k], a.f[k], a.mean_f[k],
                             a.rstd_f[k], M, D, st))
       return rc;
-    {
-      GemmGroup g{};
-      g.n = 1;
-      g.p[0] = make_gemm(kNT, Mi, D, D, a.f[k], D, w.c1_w[k], D, a.h1[k], D, w.c1_b[k], 1, nullptr, 0, false);
-      if (kp(ka + 1)) { g.p[0].keep = kp(ka + 1); g.p[0].ldk = D; g.p[0].keep_scale = ks; }
-      if (int rc = launch_group(g, st)) return rc;
-    }
-    {
-      GemmGroup g{};
-      g.n = 1;
-      g.p[0] = make_gemm(kNT, Mi, D, D, a.h1[k], D, w.c2_w[k], D, a.z, D, w.c2_b[k], 0, nullptr, 0, false);
-      if (kp(ka + 2)) { g.p[0].keep = kp(ka + 2); g.p[0].ldk = D; g.p[0].keep_scale = ks; }
-      if (int rc = launch_group(g, st)) return rc;
-    }
+    if (int rc = seq_ffn_fwd(Mi, D, a.f[k], w.c1_w[k], w.c1_b[k], w.c2_w[k], w.c2_b[k], kp(ka + 1), kp(ka + 2), ks, a.h1[k],
+                             a.z, st))
+      return rc;
     const bool last = k + 1 == nb;
-    if (int rc = tis_ln_fwd(a.f[k], a.z, seq, last ? a.x_last : a.x[k + 1], last ? w.last_w : w.ln_a_w[k + 1],
+    if (int rc = seq_ln_fwd(a.f[k], a.z, seq, last ? a.x_last : a.x[k + 1], last ? w.last_w : w.ln_a_w[k + 1],
                             last ? w.last_b : w.ln_a_b[k + 1], last ? (train ? a.feats : feats_out) : a.qn[k + 1],
                             last ? a.mean_l : a.mean_a[k + 1], last ? a.rstd_l : a.rstd_a[k + 1], M, D, st))
       return rc;
@@ -973,41 +670,22 @@ static int tis_run(const hiprec_tisasrec_shape& s, float* w_flat, float* g_flat,
   const TisParams g = tis_params(g_flat, s);
   float *T1 = a.t[0], *T2 = a.t[1], *T3 = a.t[2], *T4 = a.t[3], *T5 = a.t[4], *T6 = a.t[5], *T7 = a.t[6], *T8 = a.t[7];
   HIPREC_TRY(hipMemsetAsync(a.slab_k, 0, sizeof(float) * 2 * ((a.slab_floats + 3) / 4 * 4), st));
-  tis_loss_kernel<<<grid_for_waves(M), kBlock, 0, st>>>(a.feats, w.item_emb, pos, neg, M, D, s.n_items, a.aux, l2, T1,
-                                                        g.item_emb, scratch, stats);
-  HIPREC_TRY(hipGetLastError());
+  if (int rc = seq_loss(a.feats, w.item_emb, pos, neg, M, D, s.n_items, a.aux, l2, T1, g.item_emb, scratch, stats, st))
+    return rc;
   // T2: gradient of a block's masked output; T3: the same through that block's dropout2 keep bytes
-  if (int rc = tis_ln_bwd(T1, nullptr, a.x_last, nullptr, w.last_w, a.mean_l, a.rstd_l, nullptr, nullptr, seq,
-                          kp(kTisFixedKeep + 3 * (nb - 1) + 2), ks, T2, T3, T6, T8, g.last_w, g.last_b, a.cs, a.cs_each,
-                          M, D, st))
+  if (int rc = seq_ln_bwd(T1, nullptr, a.x_last, nullptr, w.last_w, a.mean_l, a.rstd_l, nullptr, nullptr, seq,
+                          kp(kTisFixedKeep + 3 * (nb - 1) + 2), ks, T2, T3, T6, T8, g.last_w, g.last_b, a.cs, M, D, st))
     return rc;
   for (int k = nb - 1; k >= 0; --k) {
     const int ka = kTisFixedKeep + 3 * k;
-    const float* dz = kp(ka + 2) ? T3 : T2;
-    {
-      GemmGroup q{};
-      q.n = 3;
-      q.p[0] = make_gemm(kNN, Mi, D, D, dz, D, w.c2_w[k], D, T4, D, nullptr, 0, a.h1[k], D, false);
-      if (kp(ka + 1)) { q.p[0].keep = kp(ka + 1); q.p[0].ldk = D; q.p[0].keep_scale = ks; }
-      q.p[1] = make_gemm(kTNm, D, D, Mi, dz, D, a.h1[k], D, g.c2_w[k], D, nullptr, 0, nullptr, 0, true);
-      q.p[2] = make_colsum(dz, Mi, D, D, g.c2_b[k], a.cs);
-      if (int rc = launch_group(q, st)) return rc;
-      if (int rc = launch_colsum_reduce(q, st)) return rc;
-    }
-    {
-      GemmGroup q{};
-      q.n = 3;
-      q.p[0] = make_gemm(kNN, Mi, D, D, T4, D, w.c1_w[k], D, T5, D, nullptr, 0, nullptr, 0, false);
-      q.p[1] = make_gemm(kTNm, D, D, Mi, T4, D, a.f[k], D, g.c1_w[k], D, nullptr, 0, nullptr, 0, true);
-      q.p[2] = make_colsum(T4, Mi, D, D, g.c1_b[k], a.cs);
-      if (int rc = launch_group(q, st)) return rc;
-      if (int rc = launch_colsum_reduce(q, st)) return rc;
-    }
-    // LN_f: dy = d(FFN input) + the residual's gradient; T7 = gradient of LN_a(x) + O, which is dO as well
-    if (int rc = tis_ln_bwd(T5, T2, a.qn[k], a.o[k], w.ln_f_w[k], a.mean_f[k], a.rstd_f[k], nullptr, nullptr, nullptr,
-                            nullptr, ks, T7, nullptr, T6, T8, g.ln_f_w[k], g.ln_f_b[k], a.cs, a.cs_each, M, D, st))
+    if (int rc = seq_ffn_bwd(Mi, D, kp(ka + 2) ? T3 : T2, a.f[k], a.h1[k], w.c1_w[k], w.c2_w[k], kp(ka + 1), ks, T4, T5,
+                             g.c1_w[k], g.c1_b[k], g.c2_w[k], g.c2_b[k], a.cs, st))
       return rc;
-    if (int rc = tis_by_head_width(hd, [&](auto hwc) {
+    // LN_f: dy = d(FFN input) + the residual's gradient; T7 = gradient of LN_a(x) + O, which is dO as well
+    if (int rc = seq_ln_bwd(T5, T2, a.qn[k], a.o[k], w.ln_f_w[k], a.mean_f[k], a.rstd_f[k], nullptr, nullptr, nullptr,
+                            nullptr, ks, T7, nullptr, T6, T8, g.ln_f_w[k], g.ln_f_b[k], a.cs, M, D, st))
+      return rc;
+    if (int rc = by_head_width(hd, [&](auto hwc) {
           constexpr int HD = decltype(hwc)::value;
           if (int rc2 = tis_allow_lds(reinterpret_cast<const void*>(&tis_attn_bwd_kernel<HD>), HD, hw, 1))
             return rc2;
@@ -1039,9 +717,9 @@ static int tis_run(const hiprec_tisasrec_shape& s, float* w_flat, float* g_flat,
       if (int rc = launch_colsum_reduce(q, st)) return rc;
     }
     // LN_a: dy = d(q projection input) + the residual's gradient; the K / V paths enter x directly
-    if (int rc = tis_ln_bwd(T4, T7, a.x[k], nullptr, w.ln_a_w[k], a.mean_a[k], a.rstd_a[k], T5, T1,
+    if (int rc = seq_ln_bwd(T4, T7, a.x[k], nullptr, w.ln_a_w[k], a.mean_a[k], a.rstd_a[k], T5, T1,
                             k > 0 ? seq : nullptr, k > 0 ? kp(ka - 1) : nullptr, ks, T2, T3, T6, T8, g.ln_a_w[k],
-                            g.ln_a_b[k], a.cs, a.cs_each, M, D, st))
+                            g.ln_a_b[k], a.cs, M, D, st))
       return rc;
   }
   tis_embed_bwd_kernel<<<grid_for_threads(M * D), kBlock, 0, st>>>(T2, seq, M, D, s.n_items, sqrt_d, kp(0), ks,
@@ -1078,22 +756,11 @@ extern "C" int hiprec_tisasrec_grad(const hiprec_tisasrec_shape* shape, const fl
                                     void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes,
                                     void* stream) {
   if (int rc = tis_check_shape(shape)) return rc;
-  HIPREC_REQUIRE(w_flat && seq && time_matrix && stats && workspace, "NULL pointer");
-  HIPREC_REQUIRE(batch >= 1 && seq_len >= 1 && seq_len <= shape->maxlen, "bad batch / sequence length (maxlen %d)",
-                 shape->maxlen);
-  HIPREC_REQUIRE(batch * seq_len < (1ll << 24), "batch x sequence length must stay below 2^24");
-  HIPREC_REQUIRE(batch * shape->heads <= 65535ll * 1024, "batch too large");
-  if (g_flat) {
-    HIPREC_REQUIRE(pos && neg && scratch, "training needs pos, neg and the scratch block");
-    if (scratch_bytes < kScratchBytes) {
-      set_error("scratch %zu B < %zu B", scratch_bytes, kScratchBytes);
-      return HIPREC_E_SCRATCH;
-    }
-  } else {
-    HIPREC_REQUIRE(feats_out, "forward only needs a feature buffer");
-  }
-  const size_t need = hiprec_tisasrec_workspace_bytes(shape, batch, seq_len);
-  HIPREC_REQUIRE(workspace_bytes >= need, "workspace %zu B < %zu B", workspace_bytes, need);
+  HIPREC_REQUIRE(time_matrix, "NULL pointer");
+  if (int rc = seq_check_call(w_flat, g_flat, seq, pos, neg, batch, seq_len, shape->maxlen, shape->heads, feats_out,
+                              stats, scratch, scratch_bytes, workspace, workspace_bytes,
+                              hiprec_tisasrec_workspace_bytes(shape, batch, seq_len)))
+    return rc;
   return tis_run(*shape, const_cast<float*>(w_flat), g_flat, seq, time_matrix, pos, neg, batch, seq_len, l2_emb, keep,
                  keep_scale, feats_out, stats, static_cast<Scratch*>(scratch), static_cast<float*>(workspace),
                  static_cast<hipStream_t>(stream));

@@ -216,7 +216,8 @@ def test_plumbing_and_limits():
     from beta_recsys_amd import _lib, compat
 
     assert compat.MIRRORS["beta_rec.models.sasrec"] == "sasrec"
-    assert ge.EVIDENCE_GROUPS["sasrec"] == ge._EVIDENCE_COMMON + ["sasrec.hip", "ncf.hip", "gemm.hpp"]
+    assert ge.EVIDENCE_GROUPS["sasrec"] == ge._EVIDENCE_COMMON + ["sasrec.hip", "seqrec.hip", "seqrec.hpp",
+                                                                  "ncf.hip", "gemm.hpp"]
     assert ge.evidence_group("sasrec_step") == "sasrec"
     for bad, word in ((dict(D=48, H=2), "head width"), (dict(D=256, H=4), "emb_dim"), (dict(D=64, H=2, T=300), "maxlen")):
         kw = dict(I=20, D=64, H=2, T=10, nb=1)

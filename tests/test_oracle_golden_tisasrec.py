@@ -241,7 +241,8 @@ def test_plumbing_and_limits():
     from beta_recsys_amd import _lib, compat
 
     assert compat.MIRRORS["beta_rec.models.tisasrec"] == "tisasrec"
-    assert ge.EVIDENCE_GROUPS["tisasrec"] == ge._EVIDENCE_COMMON + ["tisasrec.hip", "ncf.hip", "gemm.hpp"]
+    assert ge.EVIDENCE_GROUPS["tisasrec"] == ge._EVIDENCE_COMMON + ["tisasrec.hip", "seqrec.hip", "seqrec.hpp",
+                                                                    "ncf.hip", "gemm.hpp"]
     assert ge.evidence_group("tisasrec_step") == "tisasrec" and ge.evidence_group("sasrec_step") == "sasrec"
     for bad, word in ((dict(D=48, H=2), "head width"), (dict(D=256, H=4), "emb_dim"), (dict(D=64, H=2, T=300), "maxlen"),
                       (dict(span=257), "time_span")):
