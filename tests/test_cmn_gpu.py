@@ -12,6 +12,7 @@ import torch
 
 import cmn_numpy as cn
 import topk_reference as tk
+from cmn_edges import synthetic
 from helpers import EPS32, REL, assert_grads_as_accurate, assert_on_trajectory, assert_scalar_close, assert_sgd_exact
 from helpers import assert_step_close, assert_tensor_close, copy_state, float64_oracle, load_golden, oracle_trajectory
 from helpers import to64
@@ -269,22 +270,6 @@ def test_forward_predict_and_recommend(hip_device, case):
     got_i, got_s = eng.recommend(q, 5)
     s64 = tk.scores64(w["user_memory.weight"], w["item_memory.weight"], 1.0, None, q)
     tk.check_against_float64(got_i.cpu().numpy(), got_s.cpu().numpy(), s64, None, "recommend")
-
-
-def synthetic(U, D, lengths, B, seed, scale=0.3):
-    rng = np.random.default_rng(seed)
-    I = len(lengths)
-    lists = [rng.permutation(U)[:n] for n in lengths]
-    rowptr = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
-    col = np.concatenate(lists).astype(np.int64)
-    shapes = {"user_memory.weight": (U, D), "item_memory.weight": (I, D), "user_output.weight": (U, D),
-              "mem_layer.hop_mapping.1.weight": (D, D), "mem_layer.hop_mapping.1.bias": (D,),
-              "dense.weight": (D, 2 * D), "dense.bias": (D,), "out.weight": (1, D)}
-    w = {k: (rng.standard_normal(shapes[k]) * scale).astype(np.float32) for k in KEYS}
-    pos = np.arange(B) % I
-    neg = (pos + 1 + rng.integers(0, I - 1, B)) % I
-    users = np.array([lists[p][rng.integers(0, len(lists[p]))] for p in pos])
-    return w, rowptr, col, (users, pos, neg)
 
 
 @pytest.mark.parametrize("U,D,lengths,B", [(1600, 16, [1, 64, 65, 300, 1500], 10), (70, 7, [1, 3, 70, 64], 1),
