@@ -152,6 +152,12 @@ class TisasrecShape(Structure):
                 ("time_span", c_int32), ("n_blocks", c_int32), ("_pad", c_int32)]
 
 
+class NarmShape(Structure):
+    """hiprec_narm_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_items", c_int64), ("emb_dim", c_int32), ("hidden", c_int32), ("n_layers", c_int32), ("_pad", c_int32)]
+
+
 class T2vTables(Structure):
     """hiprec_t2v_tables (include/hiprec.h)."""
 
@@ -418,6 +424,14 @@ SIGNATURES = {
         [POINTER(TisasrecShape), _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_float, _P, c_float, _P, _P, _P, c_size_t,
          _P, c_size_t, _P],
     ),
+    "hiprec_narm_shape_bytes": (c_size_t, []),
+    "hiprec_narm_param_floats": (c_int64, [POINTER(NarmShape)]),
+    "hiprec_narm_workspace_bytes": (c_size_t, [POINTER(NarmShape), c_int64, c_int32]),
+    "hiprec_narm_grad": (
+        c_int,
+        [POINTER(NarmShape), _P, _P, _P, _P, _P, c_int64, c_int32, _P, c_float, c_float, _P, _P, _P, c_size_t, _P,
+         c_size_t, _P],
+    ),
     "hiprec_time_relation": (c_int, [_P, c_int64, c_int32, c_int32, _P, _P]),
     "hiprec_alias_sample": (c_int, [_P, _P, _P, c_int64, ctypes.c_uint64, _P, c_int64, _P]),
     "hiprec_ngcf_plan_bytes": (c_size_t, []),
@@ -606,6 +620,8 @@ def load():
         raise RuntimeError("hiprec_sasrec_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_tisasrec_shape_bytes() != ctypes.sizeof(TisasrecShape):
         raise RuntimeError("hiprec_tisasrec_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_narm_shape_bytes() != ctypes.sizeof(NarmShape):
+        raise RuntimeError("hiprec_narm_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_ncf_plan_bytes() != ctypes.sizeof(NcfPlan):
         raise RuntimeError("hiprec_ncf_plan layout mismatch between _lib.py and libhiprec.so")
     _lib = _DeviceGuardedLib(lib)

@@ -8,7 +8,7 @@ importing ``beta_rec.recommenders``.
 import sys
 
 # reference module name -> mirror module in this package.  ``beta_rec.models.torch_engine`` is NOT in
-# this table: about fifteen reference engines this package does not mirror (vbcar, narm, sgl,
+# this table: about fifteen reference engines this package does not mirror (vbcar, sgl,
 # vaecf ...) import ``ModelEngine`` from it and need the torch optimizer it builds
 # (``self.optimizer.step()``); the mirrors import their own base class relatively.
 MIRRORS = {
@@ -16,6 +16,7 @@ MIRRORS = {
     "beta_rec.models.ncf": "ncf",
     "beta_rec.models.gmf": "ncf",
     "beta_rec.models.mlp": "ncf",
+    "beta_rec.models.narm": "narm",
     "beta_rec.models.lightgcn": "lightgcn",
     "beta_rec.models.ngcf": "ngcf",
     "beta_rec.models.pairwise_gmf": "pairwise_gmf",

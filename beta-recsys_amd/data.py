@@ -233,3 +233,54 @@ class TimeSequenceSampler(SequenceSampler):
             n = min(T, times.size - 1)
             time_seq[b, T - n:] = times[-n - 1:-1]
         return users, seq, time_seq, time_relation(time_seq, self.time_span), pos, neg
+
+
+# ---- session batches for NARM (beta_rec/datasets/seq_data_utils.py) -------------------------------------------------------
+def session_prefixes(sequences):
+    """``dataset_to_seq_target_format`` (seq_data_utils.py:107-128) on a list of item sequences: for each sequence and
+    ``i = 1 .. len - 1`` the pair ``(seq[:-i], seq[-i])``, in that order.  Returns ``(out_seqs, labels)``."""
+    out_seqs, labs = [], []
+    for seq in sequences:
+        seq = list(seq)
+        for i in range(1, len(seq)):
+            labs.append(seq[-i])
+            out_seqs.append(seq[:-i])
+    return out_seqs, labs
+
+
+class SessionLoader:
+    """What ``DataLoader(SeqDataset((out_seqs, labels)), batch_size, shuffle=False, collate_fn=collate_fn)`` yields
+    (seq_data_utils.py:131-179): the batches in order; within a batch the sessions sorted by length, descending and
+    stable; the ids zero-padded to the batch's longest and time-major ``[T, B]`` int64, the labels ``[B]`` in the sorted
+    order, the lengths as a list.  Re-iterable: one loader serves every epoch.  The ragged arrays are built once; a batch
+    is cut from them with array operations only."""
+
+    def __init__(self, out_seqs, labels, batch_size):
+        if len(out_seqs) != len(labels):
+            raise ValueError("one label per session is needed")
+        if int(batch_size) < 1:
+            raise ValueError("batch_size must be >= 1")
+        self.batch_size = int(batch_size)
+        self._lens = np.fromiter((len(s) for s in out_seqs), dtype=np.int64, count=len(out_seqs))
+        if self._lens.size and int(self._lens.min()) < 1:
+            raise ValueError("every session needs at least one item")
+        self._flat = (np.concatenate([np.asarray(s, dtype=np.int64) for s in out_seqs]) if len(out_seqs)
+                      else np.zeros(0, dtype=np.int64))
+        self._start = np.concatenate([[0], np.cumsum(self._lens)[:-1]]).astype(np.int64) if len(out_seqs) else self._lens
+        self._labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+
+    def __len__(self):
+        return (self._lens.size + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        for lo in range(0, self._lens.size, self.batch_size):
+            hi = min(lo + self.batch_size, self._lens.size)
+            order = lo + np.argsort(-self._lens[lo:hi], kind="stable")
+            lens = self._lens[order]
+            T = int(lens[0])
+            pos = np.arange(T, dtype=np.int64)[None, :]
+            real = pos < lens[:, None]
+            padded = np.zeros((hi - lo, T), dtype=np.int64)
+            padded[real] = self._flat[(self._start[order][:, None] + pos)[real]]
+            yield (torch.from_numpy(np.ascontiguousarray(padded.T)), torch.from_numpy(self._labels[order].copy()),
+                   lens.tolist())

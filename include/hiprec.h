@@ -1509,6 +1509,43 @@ int hiprec_tisasrec_grad(const hiprec_tisasrec_shape* shape, const float* w_flat
 int hiprec_time_relation(const int64_t* time_seq, int64_t batch, int32_t seq_len, int32_t time_span, int32_t* out,
                          void* stream);
 
+/* ================= NARM (beta_rec/models/narm.py) ==================================================
+ * The parameters live in ONE flat buffer in state_dict() order: emb [n_items, emb_dim] (n_items counts the padding id 0;
+ * row 0 is the padding row); per layer l gru.weight_ih_l{l} [3 hidden, emb_dim or hidden], gru.weight_hh_l{l}
+ * [3 hidden, hidden], gru.bias_ih_l{l}, gru.bias_hh_l{l} [3 hidden] (gate order r, z, n); a_1, a_2 [hidden, hidden];
+ * v_t [1, hidden]; b [2 hidden, emb_dim].  hidden <= 128, emb_dim <= 128 (any value), n_layers in 1 .. 4, n_items >= 2;
+ * no limit on the catalogue or the session length beyond the workspace. */
+typedef struct hiprec_narm_shape {
+  int64_t n_items;
+  int32_t emb_dim;
+  int32_t hidden;
+  int32_t n_layers;
+  int32_t _pad;
+} hiprec_narm_shape;
+size_t hiprec_narm_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_narm_param_floats(const hiprec_narm_shape* shape);
+/* bytes of device workspace a hiprec_narm_grad call on `batch` sessions padded to `seq_len` needs (0: unsupported) */
+size_t hiprec_narm_workspace_bytes(const hiprec_narm_shape* shape, int64_t batch, int32_t seq_len);
+
+/* ---- zero_grad + forward + loss + backward of one iteration of NARMEngine.train_an_epoch (narm.py:129-142) on
+ * seq [seq_len, batch] (TIME-MAJOR as collate_fn makes it, ids in [0, n_items), 0 = padding), lens [batch] (each in
+ * [1, seq_len], any order) and target [batch]: loss = mean CrossEntropy(scores, target) over all n_items scores.
+ * Accumulates into the dense gradient g_flat (zero on entry, laid out like w_flat; the catalogue-side term of emb is
+ * written, the looked-up rows are added with row atomics, row 0 stays 0), leaves the loss partials in scratch and
+ * advances the step counter.
+ * keep: NULL (no dropout) or a HOST array of 2 device pointers, each NULL or keep bytes: the input dropout
+ * [seq_len, batch, emb_dim] (scaled by keep_scale_input) and the hidden dropout [batch, 2 hidden] on [c_local, h_T]
+ * (scaled by keep_scale_hidden).
+ * g_flat == NULL: the eval-mode forward (keep ignored, no loss; target / scratch may be NULL): query_out
+ * [batch, emb_dim] = c_t b.weight, so that scores = query_out emb^T.
+ * An id outside [0, n_items) in seq or target sets HIPREC_STATUS_ITEM_OOB and is skipped. */
+int hiprec_narm_grad(const hiprec_narm_shape* shape, const float* w_flat, float* g_flat, const int64_t* seq,
+                     const int64_t* lens, const int64_t* target, int64_t batch, int32_t seq_len,
+                     const uint8_t* const* keep, float keep_scale_input, float keep_scale_hidden, float* query_out,
+                     hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
