@@ -158,6 +158,13 @@ class NarmShape(Structure):
     _fields_ = [("n_items", c_int64), ("emb_dim", c_int32), ("hidden", c_int32), ("n_layers", c_int32), ("_pad", c_int32)]
 
 
+class VbcarShape(Structure):
+    """hiprec_vbcar_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_users", c_int64), ("n_items", c_int64), ("emb_dim", c_int32), ("late_dim", c_int32),
+                ("fea_u", c_int32), ("fea_i", c_int32), ("act", c_int32), ("_pad", c_int32)]
+
+
 class T2vTables(Structure):
     """hiprec_t2v_tables (include/hiprec.h)."""
 
@@ -432,6 +439,17 @@ SIGNATURES = {
         [POINTER(NarmShape), _P, _P, _P, _P, _P, c_int64, c_int32, _P, c_float, c_float, _P, _P, _P, c_size_t, _P,
          c_size_t, _P],
     ),
+    "hiprec_vbcar_shape_bytes": (c_size_t, []),
+    "hiprec_vbcar_param_floats": (c_int64, [POINTER(VbcarShape)]),
+    "hiprec_vbcar_workspace_bytes": (c_size_t, [POINTER(VbcarShape), c_int64, c_int32]),
+    "hiprec_vbcar_encode_workspace_bytes": (c_size_t, [POINTER(VbcarShape), c_int64, c_int32]),
+    "hiprec_vbcar_grad": (
+        c_int,
+        [POINTER(VbcarShape), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, _P, c_float, c_float, _P, _P,
+         c_size_t, _P, c_size_t, _P],
+    ),
+    "hiprec_vbcar_encode": (c_int, [POINTER(VbcarShape), _P, _P, _P, c_int64, c_int32, _P, _P, _P, c_size_t, _P]),
+    "hiprec_vbcar_predict": (c_int, [POINTER(VbcarShape), _P, _P, _P, _P, _P, c_int64, _P, _P, _P, c_size_t, _P]),
     "hiprec_time_relation": (c_int, [_P, c_int64, c_int32, c_int32, _P, _P]),
     "hiprec_alias_sample": (c_int, [_P, _P, _P, c_int64, ctypes.c_uint64, _P, c_int64, _P]),
     "hiprec_ngcf_plan_bytes": (c_size_t, []),
@@ -622,6 +640,8 @@ def load():
         raise RuntimeError("hiprec_tisasrec_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_narm_shape_bytes() != ctypes.sizeof(NarmShape):
         raise RuntimeError("hiprec_narm_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_vbcar_shape_bytes() != ctypes.sizeof(VbcarShape):
+        raise RuntimeError("hiprec_vbcar_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_ncf_plan_bytes() != ctypes.sizeof(NcfPlan):
         raise RuntimeError("hiprec_ncf_plan layout mismatch between _lib.py and libhiprec.so")
     _lib = _DeviceGuardedLib(lib)

@@ -8,7 +8,7 @@ importing ``beta_rec.recommenders``.
 import sys
 
 # reference module name -> mirror module in this package.  ``beta_rec.models.torch_engine`` is NOT in
-# this table: about fifteen reference engines this package does not mirror (vbcar, sgl,
+# this table: about fifteen reference engines this package does not mirror (tvbr, sgl,
 # vaecf ...) import ``ModelEngine`` from it and need the torch optimizer it builds
 # (``self.optimizer.step()``); the mirrors import their own base class relatively.
 MIRRORS = {
@@ -25,6 +25,7 @@ MIRRORS = {
     "beta_rec.models.tisasrec": "tisasrec",
     "beta_rec.models.triple2vec": "triple2vec",
     "beta_rec.models.ultragcn": "ultragcn",
+    "beta_rec.models.vbcar": "vbcar",
 }
 
 _MISSING = object()

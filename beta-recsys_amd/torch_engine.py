@@ -44,6 +44,10 @@ class _NullWriter:
     def add_scalar(self, tag, value, step=None):
         self.scalars.append((tag, value, step))
 
+    def add_scalars(self, main_tag, tag_scalar_dict, step=None):
+        for tag, value in tag_scalar_dict.items():
+            self.scalars.append((f"{main_tag}/{tag}", value, step))
+
     def close(self):
         pass
 

@@ -1546,6 +1546,67 @@ int hiprec_narm_grad(const hiprec_narm_shape* shape, const float* w_flat, float*
                      hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ================= VBCAR (beta_rec/models/vbcar.py) ================================================
+ * The parameters live in ONE flat buffer in state_dict() order: user_emb [n_users, emb_dim], item_emb [n_items, emb_dim],
+ * fc_u_1_mu.weight [late_dim, fea_u], .bias [late_dim], fc_u_2_mu.weight [2 emb_dim, late_dim], .bias [2 emb_dim], then
+ * fc_i_1_mu and fc_i_2_mu likewise with fea_i.  The feature matrices user_fea [n_users, fea_u] and item_fea
+ * [n_items, fea_i] (fp32, constant, 16-byte aligned) are passed beside it: they are no parameters and get no gradient.
+ * Limits: emb_dim <= 128, late_dim <= 512, feature widths <= 65536, none needing to be a multiple of anything; a step's
+ * 2 batch (1 + n_neg) item rows times the widest of (fea_u, fea_i, late_dim, 2 emb_dim) stays below 2^31. */
+enum {
+  HIPREC_VBCAR_ACT_NONE = 0,    /* any activator string the reference does not know: identity */
+  HIPREC_VBCAR_ACT_TANH = 1,
+  HIPREC_VBCAR_ACT_SIGMOID = 2,
+  HIPREC_VBCAR_ACT_RELU = 3,
+  HIPREC_VBCAR_ACT_LRELU = 4    /* F.leaky_relu's default slope 0.01 */
+};
+typedef struct hiprec_vbcar_shape {
+  int64_t n_users;
+  int64_t n_items;
+  int32_t emb_dim;
+  int32_t late_dim;
+  int32_t fea_u;
+  int32_t fea_i;
+  int32_t act;
+  int32_t _pad;
+} hiprec_vbcar_shape;
+size_t hiprec_vbcar_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_vbcar_param_floats(const hiprec_vbcar_shape* shape);
+/* bytes of device workspace a hiprec_vbcar_grad call on `batch` triples with n_neg negatives needs (0: unsupported):
+ * per side (R = batch (1 + n_neg) user rows, twice as many item rows) X [R, fea], h [R, late_dim], out [R, 2 emb_dim],
+ * d_out [R, 2 emb_dim], dh [R, late_dim] and the bias gradients' slabs */
+size_t hiprec_vbcar_workspace_bytes(const hiprec_vbcar_shape* shape, int64_t batch, int32_t n_neg);
+/* ... and what hiprec_vbcar_encode (pairs = 0) or hiprec_vbcar_predict (pairs = 1) needs for n ids / pairs */
+size_t hiprec_vbcar_encode_workspace_bytes(const hiprec_vbcar_shape* shape, int64_t n, int32_t pairs);
+
+/* ---- zero_grad + forward + loss + backward of VBCAREngine.train_single_batch (vbcar.py:111-178, 219-227) on `batch`
+ * triples (pos_u, pos_i1, pos_i2 [batch]) with neg_u, neg_i1, neg_i2 [batch, n_neg].
+ * noise [3 batch (1 + n_neg), emb_dim]: reparameterize's eps, the six blocks in the reference's order pos_u, pos_i_1,
+ * pos_i_2, neg_u, neg_i_1, neg_i_2 (the caller draws it).  scale = 1 / (3 * config batch_size), also for a short batch.
+ * Accumulates into the dense gradient g_flat (zero on entry, laid out like w_flat): the two tables with row atomics, the
+ * four Linear layers through the grouped GEMM.  Leaves the partial sums of GEN (stats.loss) and KLD (stats.reg) in
+ * scratch for hiprec_finalize_stats / the dense optimizer sweep -- the step's loss is (1 - alpha) GEN + alpha KLD -- and
+ * advances the step counter.
+ * An id outside its table sets HIPREC_STATUS_USER_OOB / HIPREC_STATUS_ITEM_OOB and is skipped (a positive id drops its
+ * triple, a negative id its own term). */
+int hiprec_vbcar_grad(const hiprec_vbcar_shape* shape, const float* w_flat, float* g_flat, const float* user_fea,
+                      const float* item_fea, const int64_t* pos_u, const int64_t* pos_i1, const int64_t* pos_i2,
+                      const int64_t* neg_u, const int64_t* neg_i1, const int64_t* neg_i2, int64_t batch, int32_t n_neg,
+                      const float* noise, float alpha, float scale, hiprec_stats* stats, void* scratch,
+                      size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The eval-mode encoder: out[k] = [mu(ids[k]) | emb[ids[k]]] as [n, 2 emb_dim]; side 0 = users (fea = user_fea),
+ * 1 = items (fea = item_fea).  An id outside its table sets the status bit and leaves NaN in its row's second half. */
+int hiprec_vbcar_encode(const hiprec_vbcar_shape* shape, const float* w_flat, const float* fea, const int64_t* ids,
+                        int64_t n, int32_t side, float* out, hiprec_stats* stats, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
+/* VBCAR.predict (vbcar.py:180-193): scores[k] = <encode(users[k]), encode(items[k])> */
+int hiprec_vbcar_predict(const hiprec_vbcar_shape* shape, const float* w_flat, const float* user_fea,
+                         const float* item_fea, const int64_t* users, const int64_t* items, int64_t n, float* scores,
+                         hiprec_stats* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,163 @@
+"""ORACLE tooling (test infrastructure): capture the VBCAR golden vectors from the REAL reference.
+
+Runs only where the reference tree exists (REFERENCE_ROOT, default: where oracle/gen_golden.py looks); the reference
+itself never travels -- only the small .npz fixtures written to tests/golden/vbcar_*.npz do.
+
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_vbcar.py
+
+Imports ``beta_rec.models.vbcar`` with the in-process shims of ``tools/gen_golden_ultragcn.py`` (the recording
+``tensorboardX`` stand-in gets the ``add_scalars`` that VBCAR's epoch loop calls) and drives the reference's own
+``VBCAREngine.train_single_batch`` on the CPU, three steps per case.
+
+A fixture is ``vbcar_<case>.npz`` (shapes, hyper-parameters, the features, the constructed weights ``winit`` for the
+fixture's torch seed, the initial weights ``w0`` = ``winit`` after ``vbcar_edges.condition``, every step's batch, its
+``eps`` as captured from ``torch.randn_like``, the losses) plus one ``vbcar_<case>_s<k>.npz`` per step k = 1 .. 3 (that
+step's gradients, the weights and the optimizer state after it).  ``replay_ok`` records whether six ``torch.randn`` from
+the step's RNG state reproduce the captured ``eps``; ``rng_state`` holds that state for the tests' ``draw_noise`` check.
+
+Asserted here at every step, with the figures printed: the batch holds every collision listed in
+``vbcar_edges.check_batch``; in the fp64 evaluation ``min |s| >= 0.25`` over every encoded row; the reference's gradients
+are within ``helpers.REL`` of their scale of the fp64 ones.
+"""
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.path.join(ROOT, "tests", "golden")
+for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import gen_golden_ultragcn as gu  # noqa: E402  (the shims and REF)
+
+N_STEPS = 3
+U, I, D, L, FU, FI, N_NEG = 9, 11, 6, 10, 7, 5, 3
+CASES = [  # name, optimizer, activator, alpha, batch, config batch_size, lr, seed
+    ("vbcar_rmsprop_tanh", "rmsprop", "tanh", 0.001, 6, 6, 1e-3, 100),
+    ("vbcar_adam_relu", "adam", "relu", 0.3, 6, 6, 1e-2, 1000),
+    ("vbcar_sgd_sigmoid_short", "sgd", "sigmoid", 0.5, 4, 6, 0.05, 2000),
+]
+
+
+def import_reference():
+    gu.import_reference()                                    # shims + sys.path
+    writer = sys.modules["tensorboardX"].SummaryWriter
+
+    def add_scalars(self, main_tag, tag_scalar_dict, step=None):
+        for tag, value in tag_scalar_dict.items():
+            self.scalars.append((f"{main_tag}/{tag}", float(value), step))
+
+    writer.add_scalars = add_scalars
+    from beta_rec.models import vbcar as ref
+
+    return ref
+
+
+def fixture(ref, name, optimizer, activator, alpha, B, batch_size, lr, seed):
+    import vbcar_edges as ve
+    import vbcar_numpy as vn
+    from helpers import REL, float64_oracle, to64
+
+    rng = np.random.default_rng(seed)
+    fea = (rng.standard_normal((U, FU)).astype(np.float32), rng.standard_normal((I, FI)).astype(np.float32))
+    torch.manual_seed(seed)
+    cfg = {"model": {"n_users": U, "n_items": I, "late_dim": L, "emb_dim": D, "n_neg": N_NEG, "batch_size": batch_size,
+                     "alpha": alpha, "activator": activator, "optimizer": optimizer, "lr": lr, "device_str": "cpu"},
+           "user_fea": fea[0], "item_fea": fea[1], "system": {"run_dir": "/tmp/hiprec_golden_runs"}}
+    eng = gu.quiet(ref.VBCAREngine, cfg)
+    assert tuple(eng.model.state_dict()) == vn.KEYS == tuple(n for n, _ in eng.model.named_parameters())
+    winit = {k: v.detach().numpy().copy() for k, v in eng.model.state_dict().items()}
+    w0 = ve.condition({k: v.copy() for k, v in winit.items()})
+    with torch.no_grad():
+        for k, prm in eng.model.named_parameters():
+            prm.copy_(torch.from_numpy(w0[k]))
+    base = {"meta": np.array([U, I, D, L, FU, FI, N_NEG, B, batch_size, N_STEPS, seed], dtype=np.int64),
+            "optimizer": np.array(optimizer), "activator": np.array(activator), "alpha": np.array(alpha),
+            "lr": np.array(lr), "user_fea": fea[0], "item_fea": fea[1]}
+    for k in vn.KEYS:
+        base[f"w0/{k}"] = w0[k]
+        base[f"winit/{k}"] = winit[k]
+    seen = []
+    orig_step = eng.optimizer.step
+
+    def capturing_step(*a, **k):
+        seen.append({n: prm.grad.detach().numpy().copy() for n, prm in eng.model.named_parameters()})
+        return orig_step(*a, **k)
+
+    eng.optimizer.step = capturing_step
+    orig_randn_like = torch.randn_like
+    drawn = []
+
+    def capturing_randn_like(x, *a, **k):
+        out = orig_randn_like(x, *a, **k)
+        drawn.append(out.detach().numpy().copy())
+        return out
+
+    scale = 1.0 / (3 * batch_size)
+    losses, kls, recs, replay_ok, sizes, batches = [], [], [], [], [], []
+    torch.randn_like = capturing_randn_like
+    try:
+        for s in range(N_STEPS):
+            batch = ve.make_batch(rng, U, I, B, N_NEG)
+            ve.check_batch(batch)
+            w_now = {k: v.detach().numpy().copy() for k, v in eng.model.state_dict().items()}
+            del drawn[:]
+            state = torch.get_rng_state()
+            loss = eng.train_single_batch(tuple(torch.from_numpy(a) for a in batch))
+            assert len(drawn) == 6 and [e.shape[0] for e in drawn] == [B] * 3 + [B * N_NEG] * 3
+            after = torch.get_rng_state()
+            torch.set_rng_state(state)
+            replay = [torch.randn(e.shape).numpy() for e in drawn]
+            torch.set_rng_state(after)
+            replay_ok.append(all(np.array_equal(a, b) for a, b in zip(replay, drawn)))
+            base[f"rng_state{s}"] = state.numpy().copy()
+            for i, e in enumerate(drawn):
+                base[f"eps{s}/{i}"] = e
+            with float64_oracle(vn):
+                l64, _, _, g64, info = vn.vbcar_grads(to64(w_now), fea, batch, drawn, alpha, scale, activator)
+            worst = max(float(np.abs(seen[-1][k] - g64[k]).max() / np.abs(g64[k]).max()) for k in vn.KEYS)
+            print(f"{name} step {s}: loss {loss:.6f} (fp64 restatement {l64:.6f}); min |s| {info['min_abs_s']:.3f}; the "
+                  f"reference's gradients are within {worst:.2e} of their scale of the exact ones")
+            assert info["min_abs_s"] >= ve.MIN_ABS_S
+            assert worst <= REL
+            assert abs(loss - l64) <= REL * abs(l64)
+            losses.append(float(loss)), kls.append(float(eng.model.kl_loss)), recs.append(float(eng.model.rec_loss))
+            step = {}
+            for k, v in eng.model.state_dict().items():
+                step[f"w/{k}"] = v.detach().numpy().copy()
+            for k, v in seen[-1].items():
+                step[f"g/{k}"] = v
+            for pname, prm in eng.model.named_parameters():
+                pst = eng.optimizer.state.get(prm, {})
+                for sk, tag in (("exp_avg", "m"), ("exp_avg_sq", "v"), ("square_avg", "v")):
+                    if sk in pst:
+                        step[f"{tag}/{pname}"] = pst[sk].detach().numpy().copy()
+            path = os.path.join(OUT, f"{name}_s{s + 1}.npz")
+            np.savez_compressed(path, **step)
+            sizes.append(os.path.getsize(path))
+            batches.append(batch)
+    finally:
+        torch.randn_like = orig_randn_like
+    for i, key in enumerate(("pos_u", "pos_i_1", "pos_i_2", "neg_u", "neg_i_1", "neg_i_2")):
+        base[key] = np.stack([b[i] for b in batches])
+    base.update(losses=np.array(losses), kl_losses=np.array(kls), rec_losses=np.array(recs),
+                replay_ok=np.array(replay_ok))
+    path = os.path.join(OUT, name + ".npz")
+    np.savez_compressed(path, **base)
+    print(f"{name}: optimizer {optimizer}, losses {losses}; six torch.randn from the step's RNG state reproduce eps in "
+          f"{sum(replay_ok)} of {len(replay_ok)} steps")
+    print(f"{name}: {os.path.getsize(path) / 1024:.0f} KiB + steps {[f'{s / 1024:.0f} KiB' for s in sizes]}")
+    assert max(sizes + [os.path.getsize(path)]) < 500_000
+
+
+def main():
+    ref = import_reference()
+    for case in CASES:
+        fixture(ref, *case)
+
+
+if __name__ == "__main__":
+    main()
