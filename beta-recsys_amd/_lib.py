@@ -165,6 +165,13 @@ class VbcarShape(Structure):
                 ("fea_u", c_int32), ("fea_i", c_int32), ("act", c_int32), ("_pad", c_int32)]
 
 
+class VaecfShape(Structure):
+    """hiprec_vaecf_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_users", c_int64), ("n_items", c_int64), ("z_dim", c_int32), ("n_hidden", c_int32),
+                ("hidden", c_int32 * 3), ("act", c_int32), ("likelihood", c_int32), ("w0_shadow", c_int32)]
+
+
 class T2vTables(Structure):
     """hiprec_t2v_tables (include/hiprec.h)."""
 
@@ -450,6 +457,18 @@ SIGNATURES = {
     ),
     "hiprec_vbcar_encode": (c_int, [POINTER(VbcarShape), _P, _P, _P, c_int64, c_int32, _P, _P, _P, c_size_t, _P]),
     "hiprec_vbcar_predict": (c_int, [POINTER(VbcarShape), _P, _P, _P, _P, _P, c_int64, _P, _P, _P, c_size_t, _P]),
+    "hiprec_vaecf_shape_bytes": (c_size_t, []),
+    "hiprec_vaecf_param_floats": (c_int64, [POINTER(VaecfShape)]),
+    "hiprec_vaecf_workspace_bytes": (c_size_t, [POINTER(VaecfShape), c_int64, c_int64]),
+    "hiprec_vaecf_encode_workspace_bytes": (c_size_t, [POINTER(VaecfShape), c_int64]),
+    "hiprec_vaecf_decode_workspace_bytes": (c_size_t, [POINTER(VaecfShape), c_int64]),
+    "hiprec_vaecf_grad": (
+        c_int,
+        [POINTER(VaecfShape), _P, _P, _P, _P, _P, c_int64, c_int64, _P, c_float, _P, _P, c_size_t, _P, c_size_t, _P],
+    ),
+    "hiprec_vaecf_encode": (c_int, [POINTER(VaecfShape), _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_size_t, _P]),
+    "hiprec_vaecf_decode_at": (
+        c_int, [POINTER(VaecfShape), _P, _P, c_int64, _P, _P, c_int64, _P, _P, _P, _P, c_size_t, _P]),
     "hiprec_time_relation": (c_int, [_P, c_int64, c_int32, c_int32, _P, _P]),
     "hiprec_alias_sample": (c_int, [_P, _P, _P, c_int64, ctypes.c_uint64, _P, c_int64, _P]),
     "hiprec_ngcf_plan_bytes": (c_size_t, []),
@@ -642,6 +661,8 @@ def load():
         raise RuntimeError("hiprec_narm_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vbcar_shape_bytes() != ctypes.sizeof(VbcarShape):
         raise RuntimeError("hiprec_vbcar_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_vaecf_shape_bytes() != ctypes.sizeof(VaecfShape):
+        raise RuntimeError("hiprec_vaecf_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_ncf_plan_bytes() != ctypes.sizeof(NcfPlan):
         raise RuntimeError("hiprec_ncf_plan layout mismatch between _lib.py and libhiprec.so")
     _lib = _DeviceGuardedLib(lib)

@@ -9,7 +9,7 @@ import sys
 
 # reference module name -> mirror module in this package.  ``beta_rec.models.torch_engine`` is NOT in
 # this table: about fifteen reference engines this package does not mirror (tvbr, sgl,
-# vaecf ...) import ``ModelEngine`` from it and need the torch optimizer it builds
+# lcfn ...) import ``ModelEngine`` from it and need the torch optimizer it builds
 # (``self.optimizer.step()``); the mirrors import their own base class relatively.
 MIRRORS = {
     "beta_rec.models.mf": "mf",
@@ -26,6 +26,7 @@ MIRRORS = {
     "beta_rec.models.triple2vec": "triple2vec",
     "beta_rec.models.ultragcn": "ultragcn",
     "beta_rec.models.vbcar": "vbcar",
+    "beta_rec.models.vaecf": "vaecf",
 }
 
 _MISSING = object()

@@ -196,6 +196,23 @@ class SequenceSampler:
         """The reference's sampler owns worker processes; this one owns nothing."""
 
 
+def instance_vae_loader(users, items, n_users, n_items):
+    """``(user_indices, matrix)`` as base_data.py:513-532 hands them to ``VAECFEngine.train_an_epoch``: the ids of the
+    users that occur, ascending, and the ``[n_users, n_items]`` scipy CSR matrix of the interactions (one per distinct
+    pair; the epoch loop binarises it anyway)."""
+    from scipy.sparse import csr_matrix
+
+    u = np.asarray(users.cpu() if torch.is_tensor(users) else users, dtype=np.int64).reshape(-1)
+    i = np.asarray(items.cpu() if torch.is_tensor(items) else items, dtype=np.int64).reshape(-1)
+    if u.shape != i.shape:
+        raise ValueError("users and items differ in length")
+    if u.size and (u.min() < 0 or u.max() >= n_users or i.min() < 0 or i.max() >= n_items):
+        raise IndexError("training frame holds a user / item id outside [0, n_users) x [0, n_items)")
+    matrix = csr_matrix((np.ones(len(u), dtype=np.float32), (u, i)), shape=(n_users, n_items))
+    matrix.data[:] = 1.0
+    return np.unique(u), matrix
+
+
 def time_relation(time_seq, time_span):
     """The reference's ``computeRePos`` (beta_rec/recommenders/tisasrec.py:108-127) for one ``[T]`` sequence or a batch
     ``[B, T]`` of them: ``min(|t_i - t_j|, time_span)`` as int32 ``[..., T, T]``."""

@@ -1607,6 +1607,75 @@ int hiprec_vbcar_predict(const hiprec_vbcar_shape* shape, const float* w_flat, c
                          const float* item_fea, const int64_t* users, const int64_t* items, int64_t n, float* scores,
                          hiprec_stats* stats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ================= VAECF / Mult-VAE (beta_rec/models/vaecf.py) =====================================
+ * The parameters live in ONE flat buffer in state_dict() order: encoder.fc{l}.weight [hidden[l], hidden[l-1]] (fc0:
+ * [hidden[0], n_items]) and .bias for l = 0 .. n_hidden-1, enc_mu.weight [z_dim, hidden[n_hidden-1]], .bias,
+ * enc_logvar likewise, then decoder.fc{l} over the widths z_dim, hidden[n_hidden-1], ..., hidden[0], n_items (the last
+ * one, [n_items, hidden[0]], has no activation behind it).
+ * A batch of rows is CSR: row_ptr[batch + 1] (row_ptr[0] may be any offset into items / values), items[nnz] (int64,
+ * unique within a row) and values[nnz] (fp32).  No [batch, n_items] buffer exists anywhere.
+ * Limits: 1 <= z_dim <= 256, 1 .. 3 hidden layers of 1 .. 512 columns, any n_items >= 1, any batch >= 1 below 2^22
+ * rows; rows without nonzeros are fine. */
+enum {
+  HIPREC_VAECF_ACT_SIGMOID = 0,
+  HIPREC_VAECF_ACT_TANH = 1,
+  HIPREC_VAECF_ACT_RELU = 2,
+  HIPREC_VAECF_ACT_RELU6 = 3
+};
+enum {
+  HIPREC_VAECF_LIK_MULT = 0, /* softmax;  ll = x log(p + 1e-10) */
+  HIPREC_VAECF_LIK_BERN = 1, /* sigmoid;  ll = x log(p + 1e-10) + (1 - x) log(1 - p + 1e-10) */
+  HIPREC_VAECF_LIK_GAUS = 2, /* sigmoid;  ll = -(x - p)^2 */
+  HIPREC_VAECF_LIK_POIS = 3  /* sigmoid;  ll = x log(p + 1e-10) - p */
+};
+typedef struct hiprec_vaecf_shape {
+  int64_t n_users;
+  int64_t n_items;
+  int32_t z_dim;
+  int32_t n_hidden;
+  int32_t hidden[3];
+  int32_t act;
+  int32_t likelihood;
+  int32_t w0_shadow; /* 0: the first layer gathers the columns of encoder.fc0.weight as they lie (stride n_items);
+                      * 1: from a transposed copy in the workspace that every call refreshes */
+} hiprec_vaecf_shape;
+size_t hiprec_vaecf_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_vaecf_param_floats(const hiprec_vaecf_shape* shape);
+/* bytes of device workspace of a hiprec_vaecf_grad call on `batch` rows holding nnz nonzeros (0: unsupported, and
+ * hiprec_last_error says why): the [batch, width] activations and their gradients, per row and item split the
+ * log-sum-exp and likelihood parts, the bias gradients' slabs and, with w0_shadow, [n_items, hidden[0]] */
+size_t hiprec_vaecf_workspace_bytes(const hiprec_vaecf_shape* shape, int64_t batch, int64_t nnz);
+size_t hiprec_vaecf_encode_workspace_bytes(const hiprec_vaecf_shape* shape, int64_t n_rows);
+size_t hiprec_vaecf_decode_workspace_bytes(const hiprec_vaecf_shape* shape, int64_t n_rows);
+
+/* ---- zero_grad + forward + loss + backward of VAECFEngine.train_single_batch (vaecf.py:61-87, 134-142) on `batch` CSR
+ * rows; noise [batch, z_dim] is reparameterize's eps (the caller draws it).  loss = mean_b(beta kld_b - ll_b) over the
+ * rows of THIS batch.  Accumulates into the dense gradient g_flat (zero on entry, laid out like w_flat): the first layer
+ * over the nonzeros only (a column no row touches keeps an exactly zero gradient), the last layer tile by tile from Hd
+ * [batch, hidden[0]], the layers between through the grouped GEMM.  Leaves the partial sums of mean ll (stats.loss) and
+ * mean kld (stats.reg) in scratch for hiprec_finalize_stats / the dense optimizer sweep -- the step's loss is
+ * beta * reg - loss -- and advances the step counter.
+ * An item outside [0, n_items) sets HIPREC_STATUS_ITEM_OOB and is skipped; a row_ptr that does not fit nnz sets
+ * HIPREC_STATUS_ROW_OOB and its row counts as empty. */
+int hiprec_vaecf_grad(const hiprec_vaecf_shape* shape, const float* w_flat, float* g_flat, const int64_t* row_ptr,
+                      const int64_t* items, const float* values, int64_t batch, int64_t nnz, const float* noise,
+                      float beta, hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
+/* The inference encoder: mu [n_rows, z_dim] of the CSR rows, and hd [n_rows, hidden[0]] = the decoder's last hidden
+ * activation at z = mu, whose product with decoder.fc{n_hidden} gives the logits of the whole catalogue. */
+int hiprec_vaecf_encode(const hiprec_vaecf_shape* shape, const float* w_flat, const int64_t* row_ptr,
+                        const int64_t* items, const float* values, int64_t n_rows, int64_t nnz, float* mu, float* hd,
+                        hiprec_stats* stats, void* workspace, size_t workspace_bytes, void* stream);
+
+/* out[k] = the decoded probability at (rows[k], items[k]) from hd [n_rows, hidden[0]]: softmax over the catalogue for
+ * mult (the rows' log-sum-exps are computed tile by tile and, when lse_out [n_rows] is given, handed out), sigmoid
+ * otherwise.  A row outside [0, n_rows) or an item outside the catalogue sets its status bit and yields NaN. */
+int hiprec_vaecf_decode_at(const hiprec_vaecf_shape* shape, const float* w_flat, const float* hd, int64_t n_rows,
+                           const int64_t* rows, const int64_t* items, int64_t n, float* out, float* lse_out,
+                           hiprec_stats* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
