@@ -20,6 +20,7 @@ from .narm import NARM, NARMEngine  # noqa: F401
 from .triple2vec import Triple2vec, Triple2vecEngine  # noqa: F401
 from .vbcar import VBCAR, VBCAREngine  # noqa: F401
 from .vaecf import VAE, VAECFEngine  # noqa: F401
+from .tvbr import TVBR, TVBREngine  # noqa: F401
 from .ultragcn import UltraGCN, UltraGCNEngine, get_ii_constraint_mat  # noqa: F401
 from . import eval  # noqa: F401,A004  (evaluate / predict / rank_metrics)
 from . import data  # noqa: F401  (device-side loaders / negative sampling)

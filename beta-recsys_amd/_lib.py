@@ -23,6 +23,7 @@ STATUS_USER_OOB, STATUS_ITEM_OOB, STATUS_ROW_OOB, STATUS_ROUTE_OVERFLOW = 1, 2, 
 STATUS_NEG_EXHAUSTED = 16
 STATUS_LAZY_TABLE = 32
 STATUS_TABLE_FULL = 64
+STATUS_TIME_OOB = 128
 
 
 class MfTables(Structure):
@@ -162,6 +163,13 @@ class VbcarShape(Structure):
     """hiprec_vbcar_shape (include/hiprec.h)."""
 
     _fields_ = [("n_users", c_int64), ("n_items", c_int64), ("emb_dim", c_int32), ("late_dim", c_int32),
+                ("fea_u", c_int32), ("fea_i", c_int32), ("act", c_int32), ("_pad", c_int32)]
+
+
+class TvbrShape(Structure):
+    """hiprec_tvbr_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_users", c_int64), ("n_items", c_int64), ("emb_dim", c_int32), ("time_step", c_int32),
                 ("fea_u", c_int32), ("fea_i", c_int32), ("act", c_int32), ("_pad", c_int32)]
 
 
@@ -457,6 +465,17 @@ SIGNATURES = {
     ),
     "hiprec_vbcar_encode": (c_int, [POINTER(VbcarShape), _P, _P, _P, c_int64, c_int32, _P, _P, _P, c_size_t, _P]),
     "hiprec_vbcar_predict": (c_int, [POINTER(VbcarShape), _P, _P, _P, _P, _P, c_int64, _P, _P, _P, c_size_t, _P]),
+    "hiprec_tvbr_shape_bytes": (c_size_t, []),
+    "hiprec_tvbr_param_floats": (c_int64, [POINTER(TvbrShape)]),
+    "hiprec_tvbr_workspace_bytes": (c_size_t, [POINTER(TvbrShape), c_int64, c_int32]),
+    "hiprec_tvbr_encode_workspace_bytes": (c_size_t, [POINTER(TvbrShape), c_int64, c_int32]),
+    "hiprec_tvbr_grad": (
+        c_int,
+        [POINTER(TvbrShape), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, _P, c_float, c_float, _P,
+         _P, c_size_t, _P, c_size_t, _P],
+    ),
+    "hiprec_tvbr_encode": (c_int, [POINTER(TvbrShape), _P, _P, _P, c_int64, c_int32, _P, _P, _P, c_size_t, _P]),
+    "hiprec_tvbr_predict": (c_int, [POINTER(TvbrShape), _P, _P, _P, _P, _P, c_int64, _P, _P, _P, c_size_t, _P]),
     "hiprec_vaecf_shape_bytes": (c_size_t, []),
     "hiprec_vaecf_param_floats": (c_int64, [POINTER(VaecfShape)]),
     "hiprec_vaecf_workspace_bytes": (c_size_t, [POINTER(VaecfShape), c_int64, c_int64]),
@@ -661,6 +680,8 @@ def load():
         raise RuntimeError("hiprec_narm_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vbcar_shape_bytes() != ctypes.sizeof(VbcarShape):
         raise RuntimeError("hiprec_vbcar_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_tvbr_shape_bytes() != ctypes.sizeof(TvbrShape):
+        raise RuntimeError("hiprec_tvbr_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vaecf_shape_bytes() != ctypes.sizeof(VaecfShape):
         raise RuntimeError("hiprec_vaecf_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_ncf_plan_bytes() != ctypes.sizeof(NcfPlan):

@@ -8,7 +8,7 @@ importing ``beta_rec.recommenders``.
 import sys
 
 # reference module name -> mirror module in this package.  ``beta_rec.models.torch_engine`` is NOT in
-# this table: about fifteen reference engines this package does not mirror (tvbr, sgl,
+# this table: about fifteen reference engines this package does not mirror (sgl,
 # lcfn ...) import ``ModelEngine`` from it and need the torch optimizer it builds
 # (``self.optimizer.step()``); the mirrors import their own base class relatively.
 MIRRORS = {
@@ -27,6 +27,7 @@ MIRRORS = {
     "beta_rec.models.ultragcn": "ultragcn",
     "beta_rec.models.vbcar": "vbcar",
     "beta_rec.models.vaecf": "vaecf",
+    "beta_rec.models.tvbr": "tvbr",
 }
 
 _MISSING = object()

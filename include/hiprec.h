@@ -47,6 +47,7 @@ extern "C" {
 #define HIPREC_STATUS_LAZY_TABLE 32u    /* lazy Adam: a step beyond the scalars table whose bias corrections still move */
 #define HIPREC_STATUS_TABLE_FULL 64u    /* a batch's contribution hash partition overflowed: some row's gradient parts were
                                          * not listed (hiprec_batch_row_contrib flags the batch, the step that uses it raises) */
+#define HIPREC_STATUS_TIME_OOB 128u     /* TVBR: a row's time step outside [0, time_step) */
 
 /* optimizer kinds, beta_rec/models/torch_engine.py:23-39 (only `lr` is ever set there) */
 #define HIPREC_OPT_SGD 0
@@ -1606,6 +1607,75 @@ int hiprec_vbcar_encode(const hiprec_vbcar_shape* shape, const float* w_flat, co
 int hiprec_vbcar_predict(const hiprec_vbcar_shape* shape, const float* w_flat, const float* user_fea,
                          const float* item_fea, const int64_t* users, const int64_t* items, int64_t n, float* scores,
                          hiprec_stats* stats, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ================= TVBR (beta_rec/models/tvbr.py) ==================================================
+ * The parameters live in ONE flat buffer in state_dict() order: user_emb [n_users, emb_dim], item_emb [n_items, emb_dim],
+ * time_embdding [time_step + 1, time_step + 1], user_mean, user_std [n_users, emb_dim], item_mean, item_std [n_items,
+ * emb_dim], then the four encoders time2mean_u, time2std_u (K = emb_dim + time_step + 1 + fea_u), time2mean_i, time2std_i
+ * (K with fea_i): .0.weight [emb_dim, K], .0.bias [emb_dim] and, under prelu only, .1.weight [1].  The columns of an
+ * encoder weight are [table row | time row | feature row], as the reference concatenates them.  The feature matrices
+ * user_fea [n_users, fea_u] and item_fea [n_items, fea_i] (fp32, constant) are passed beside it.
+ * Limits: emb_dim <= 128, feature widths <= 65536, 1 <= time_step <= 255; a step's 2 batch (1 + n_neg) item rows times
+ * the wider K stays below 2^31. */
+enum {
+  HIPREC_TVBR_ACT_TANH = 1,
+  HIPREC_TVBR_ACT_HARDTANH = 2,
+  HIPREC_TVBR_ACT_LOGSIGMOID = 3,
+  HIPREC_TVBR_ACT_SIGMOID = 4,
+  HIPREC_TVBR_ACT_RELU = 5,
+  HIPREC_TVBR_ACT_LRELU = 6,    /* nn.LeakyReLU's default slope 0.01 */
+  HIPREC_TVBR_ACT_PRELU = 7     /* one trainable slope per encoder */
+};
+typedef struct hiprec_tvbr_shape {
+  int64_t n_users;
+  int64_t n_items;
+  int32_t emb_dim;
+  int32_t time_step;
+  int32_t fea_u;
+  int32_t fea_i;
+  int32_t act;
+  int32_t _pad;
+} hiprec_tvbr_shape;
+size_t hiprec_tvbr_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_tvbr_param_floats(const hiprec_tvbr_shape* shape);
+/* bytes of device workspace a hiprec_tvbr_grad call on `batch` triples with n_neg negatives needs (0: unsupported): the
+ * four [time_step + 1, emb_dim] time tables and their gradients, and per side (R = batch (1 + n_neg) user rows, twice as
+ * many item rows) two X [R, K], two base [R, emb_dim], four activations and their gradients [R, emb_dim], two table-row
+ * gradients [R, emb_dim] and the bias gradients' slabs */
+size_t hiprec_tvbr_workspace_bytes(const hiprec_tvbr_shape* shape, int64_t batch, int32_t n_neg);
+/* ... and what hiprec_tvbr_encode (pairs = 0) or hiprec_tvbr_predict (pairs = 1) needs for n ids / pairs */
+size_t hiprec_tvbr_encode_workspace_bytes(const hiprec_tvbr_shape* shape, int64_t n, int32_t pairs);
+
+/* ---- zero_grad + forward + loss + backward of TVBREngine.train_single_batch (tvbr.py:242-369, 449-465) on `batch`
+ * triples (pos_u, pos_i1, pos_i2, pos_t [batch]) with neg_u, neg_i1, neg_i2, neg_t [batch, n_neg]: row k of the prior
+ * reads time row t[k], of the posterior time row t[k] + 1, every row with its own t.
+ * noise [3 batch (1 + n_neg), emb_dim]: reparameterize's eps, the six blocks in the reference's order pos_u, pos_i_1,
+ * pos_i_2, neg_u, neg_i_1, neg_i_2 (the caller draws it).  scale = 1 / (3 * config batch_size), also for a short batch;
+ * it divides rec_loss only.
+ * Accumulates into the dense gradient g_flat (zero on entry, laid out like w_flat).  Leaves the partial sums of rec_loss
+ * (stats.loss) and kl_loss (stats.reg) in scratch for hiprec_finalize_stats / the dense optimizer sweep -- the step's
+ * loss is (1 - alpha) rec_loss + alpha kl_loss -- and advances the step counter.
+ * An id outside its table sets HIPREC_STATUS_USER_OOB / HIPREC_STATUS_ITEM_OOB, a t outside [0, time_step) sets
+ * HIPREC_STATUS_TIME_OOB; either is skipped (on a positive row its triple, on a negative row its own term). */
+int hiprec_tvbr_grad(const hiprec_tvbr_shape* shape, const float* w_flat, float* g_flat, const float* user_fea,
+                     const float* item_fea, const int64_t* pos_u, const int64_t* pos_i1, const int64_t* pos_i2,
+                     const int64_t* neg_u, const int64_t* neg_i1, const int64_t* neg_i2, const int64_t* pos_t,
+                     const int64_t* neg_t, int64_t batch, int32_t n_neg, const float* noise, float alpha, float scale,
+                     hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
+/* The eval-mode encoder (tvbr.py:371-407): out[k] = [posterior mean of ids[k] at t = time_step | emb[ids[k]]] as
+ * [n, 2 emb_dim]; side 0 = users (fea = user_fea), 1 = items (fea = item_fea).  An id outside its table sets the status
+ * bit and leaves NaN in its row's second half. */
+int hiprec_tvbr_encode(const hiprec_tvbr_shape* shape, const float* w_flat, const float* fea, const int64_t* ids,
+                       int64_t n, int32_t side, float* out, hiprec_stats* stats, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* TVBR.predict (tvbr.py:371-412): scores[k] = <encode(users[k]), encode(items[k])> */
+int hiprec_tvbr_predict(const hiprec_tvbr_shape* shape, const float* w_flat, const float* user_fea,
+                        const float* item_fea, const int64_t* users, const int64_t* items, int64_t n, float* scores,
+                        hiprec_stats* stats, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ================= VAECF / Mult-VAE (beta_rec/models/vaecf.py) =====================================
  * The parameters live in ONE flat buffer in state_dict() order: encoder.fc{l}.weight [hidden[l], hidden[l-1]] (fc0:
