@@ -511,6 +511,19 @@ SIGNATURES = {
         c_int,
         [_P, c_int64, c_int32, _P, _P, POINTER(c_int32), c_int32, _P, c_size_t, _P, _P],
     ),
+    "hiprec_knn_workspace_bytes": (c_size_t, [c_int32, c_int64, c_int64, c_int64, c_int32]),
+    "hiprec_knn_item_similarity": (
+        c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int32, _P, c_size_t, _P]),
+    "hiprec_knn_item_scores": (
+        c_int,
+        [_P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, c_int32, _P, _P, _P, _P, c_int32, _P, c_size_t,
+         _P, _P],
+    ),
+    "hiprec_knn_user_scores": (
+        c_int,
+        [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int32, _P, c_int64, _P, _P, _P, _P, _P, c_int32, _P, _P, _P, _P,
+         c_int32, _P, c_size_t, _P, _P],
+    ),
     "hiprec_stage_epoch": (c_int, [_P, _P, _P, c_int32, _P, c_int64, c_int64, _P, _P, _P, _P]),
     "hiprec_stage_epoch_shuffled": (c_int, [_P, _P, _P, c_int32, ctypes.c_uint64, c_int64, c_int64, _P, _P, _P, _P]),
     "hiprec_mf_bce_epoch": (

@@ -28,6 +28,8 @@ MIRRORS = {
     "beta_rec.models.vbcar": "vbcar",
     "beta_rec.models.vaecf": "vaecf",
     "beta_rec.models.tvbr": "tvbr",
+    "beta_rec.models.itemKNN": "knn",
+    "beta_rec.models.userKNN": "knn",
 }
 
 _MISSING = object()

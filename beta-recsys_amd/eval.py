@@ -153,7 +153,7 @@ def evaluate_full(model, test_df, train_df=None, metrics=RANK_METRICS, k_li=(5, 
     rows is no candidate and does not count), and the metrics are those of :func:`evaluate`, in its
     ``{f"{metric}@{k}": value}`` form and key order.  Computed as ``recommend`` at ``max(k_li)`` followed by
     ``hiprec_topk_metrics``: no candidate frame and no score matrix is built.  ``model``: a model with
-    ``ranking_factors()`` or its engine."""
+    ``ranking_factors()`` or ``topk_items()`` (see ``recommend.recommend``), or its engine."""
     from .recommend import ranking_factors, topk_factors    # (recommend imports data, which imports this module)
 
     unknown = [m for m in metrics if m not in RANK_METRICS]
@@ -167,9 +167,14 @@ def evaluate_full(model, test_df, train_df=None, metrics=RANK_METRICS, k_li=(5, 
         if hasattr(engine, "flush_lazy"):
             engine.flush_lazy()
         model = engine.model
-    U, I, alpha, bias = ranking_factors(model)
-    dev = U.device
-    n_users, n_items = int(U.shape[0]), int(I.shape[0])
+    topk_hook = getattr(model, "topk_items", None)   # a model that ranks by its own kernel (the neighbourhood models)
+    if topk_hook is not None:
+        dev = model.seen_csr()[0].device
+        n_users, n_items = int(model.n_users), int(model.n_items)
+    else:
+        U, I, alpha, bias = ranking_factors(model)
+        dev = U.device
+        n_users, n_items = int(U.shape[0]), int(I.shape[0])
     as_ids = lambda col: torch.as_tensor(np.asarray(col)).to(dev, torch.int64).reshape(-1)  # noqa: E731
     t_users, t_items = as_ids(_column(test_df, DEFAULT_USER_COL)), as_ids(_column(test_df, DEFAULT_ITEM_COL))
     try:
@@ -191,7 +196,10 @@ def evaluate_full(model, test_df, train_df=None, metrics=RANK_METRICS, k_li=(5, 
     if query.numel() and (int(query.min()) < 0 or int(query.max()) >= n_users):
         raise IndexError("test frame holds a user id outside [0, n_users)")
     k_max = max(k_li)
-    items, _ = topk_factors(U, I, alpha, bias, query, k_max, seen, item_splits)
+    if topk_hook is not None:
+        items, _ = topk_hook(query, k_max, seen, item_splits)
+    else:
+        items, _ = topk_factors(U, I, alpha, bias, query, k_max, seen, item_splits)
     # the truth rows of the query users, in query order: a CSR over the same pos array needs its rows contiguous, so
     # gather the lengths and rebuild the pointer; the rows themselves are copied in order
     lens = truth_ptr_all[query + 1] - truth_ptr_all[query]

@@ -137,7 +137,8 @@ def recommend(model, users, k, seen=None, item_splits=0):
     catalogue by the model's ranking score, best first (ties to the lower item id), never an item of the user's ``seen``
     row; a user with fewer than ``k`` unseen items gets ``-1`` / ``-inf`` in the tail.
 
-    ``model``: a model with ``ranking_factors()`` (MF, LightGCN, NGCF, UltraGCN) or an engine holding one.
+    ``model``: a model with ``ranking_factors()`` (MF, LightGCN, NGCF, UltraGCN) or an engine holding one; a model that
+    defines ``topk_items(users, k, seen, item_splits)`` (ItemKNN, UserKNN: csrc/knn.hip) is ranked through that instead.
     ``seen``: None, a ``(user_ptr, pos_sorted)`` pair or a ``(users, items)`` pair of id columns (the training frame);
     what :func:`normalise_seen` returns is taken without being checked again.
     ``item_splits``: into how many item ranges the catalogue is cut to fill the chip (0 = chosen by the library); the
@@ -148,5 +149,8 @@ def recommend(model, users, k, seen=None, item_splits=0):
         if flush is not None:
             flush()                    # a lazy optimizer's lagging rows, as predict does
         model = engine.model
+    hook = getattr(model, "topk_items", None)     # a model that ranks by its own kernel (the neighbourhood models)
+    if hook is not None:
+        return hook(users, k, seen, item_splits)
     U, I, alpha, bias = ranking_factors(model)
     return topk_factors(U, I, alpha, bias, users, k, seen, item_splits)

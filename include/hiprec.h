@@ -1093,6 +1093,61 @@ int hiprec_topk_metrics(const int64_t* items, int64_t n_query, int32_t k, const 
                         const int64_t* truth_sorted, const int32_t* k_list_host, int32_t n_k, double* workspace,
                         size_t workspace_bytes, double* out, void* stream);
 
+/* ================= ItemKNN / UserKNN: neighbourhood recommenders (csrc/knn.hip) ====
+ * models/itemKNN.py and models/userKNN.py without their scipy loops.  B is the [n_users, n_items] interaction matrix
+ * with multiplicities (a pair that occurs m times has value m), handed over as two CSRs, B (b_*: one row per user)
+ * and B^T (bt_*: one row per item): ptr device int64 [rows + 1], idx device int64 ascending and unique per row, val
+ * device fp32 (the integer multiplicity).  cnt[n_items] / cu[n_users]: device fp64 column / row sums of B.
+ *
+ *   ItemKNN   S[i, j] = (float)(overlap_i[j] / sqrt(cnt[j])),  overlap_i[j] = sum over the distinct users v of column i
+ *             of B[v, j] (an exact integer; 0 stays 0);  score_u[j] = fp32 sum of S[i, j] over the user's distinct
+ *             items i in ascending order;  nothing is masked.
+ *   UserKNN   sim_u[v] = overlap_u[v] / sqrt(cu[v]) in fp64 (correctly rounded divide and square root),
+ *             overlap_u[v] = sum over the distinct items j of user u of B[v, j];  the `k` neighbours are the users with
+ *             the largest sim, ties to the lower id, users with sim 0 (lowest ids first) when fewer overlap;
+ *             score_u[j] = fp64 sum over the neighbours, best first, of sim[v] * B[v, j];  the user's own items are -inf.
+ *
+ * One block owns one row of S / one query user, so every sum has one owner and a fixed order: no device-scope atomics,
+ * the same bits on every run.  The block's dense accumulator ([n_users] overlaps, [n_items] scores) lives in LDS while
+ * max(n_users, n_items) (item_similarity, item_scores: n_items) <= lds_cap entries; beyond that in the block's slice of
+ * `workspace`, which is cleared through the list of entries the block touched.  lds_cap: 0 = HIPREC_KNN_LDS_CAP (its
+ * largest value), 1 = always the workspace form; the result does not depend on it.
+ *
+ * Output stage of the two score entry points (either or both):
+ *   pairs   pair_ptr[n_query + 1] / pair_items (device int64): out_pick[p] = score_{query[q]}[pair_items[p]] for p in
+ *           pair_ptr[q] .. pair_ptr[q + 1]  (fp32 for ItemKNN, fp64 for UserKNN).  pair_ptr NULL = none.  An item
+ *           outside [0, n_items) sets HIPREC_STATUS_ITEM_OOB and yields 0.
+ *   top-K   topk >= 1: out_items / out_scores [n_query, topk], hiprec_topk_recommend's rules: best first by the fp32
+ *           score (UserKNN: the fp64 score rounded to fp32), ties to the lower item id, -0 == +0, never an item of the
+ *           user's row of the seen CSR (seen_ptr[n_users + 1] / seen_idx, both NULL = nothing masked) nor one whose
+ *           score is -inf, -1 / -inf in the tail.  topk 0 = none.
+ * A query id outside [0, n_users) sets HIPREC_STATUS_USER_OOB; its picks are 0, its list -1 / -inf, its neighbours -1 / 0.
+ * Limits: 1 <= k <= HIPREC_KNN_MAX_K (k <= n_users), 0 <= topk <= HIPREC_KNN_MAX_K, n_users, n_items < 2^31.
+ * workspace: hiprec_knn_workspace_bytes(op, ...) bytes (0 in the LDS form; (size_t)-1 for bad sizes). */
+#define HIPREC_KNN_MAX_K 128
+#define HIPREC_KNN_LDS_CAP 7168 /* 56 KB of 64-bit entries: what a block gets without asking for more, less its lists */
+#define HIPREC_KNN_OP_ITEM_SIMILARITY 0
+#define HIPREC_KNN_OP_ITEM_SCORES 1
+#define HIPREC_KNN_OP_USER_SCORES 2
+size_t hiprec_knn_workspace_bytes(int32_t op, int64_t n_users, int64_t n_items, int64_t n_query, int32_t lds_cap);
+/* S [n_items, n_items] fp32 with leading dimension lds >= n_items; every entry is written (rows without users: zeros) */
+int hiprec_knn_item_similarity(const int64_t* bt_ptr, const int64_t* bt_idx, const int64_t* b_ptr, const int64_t* b_idx,
+                               const float* b_val, const double* cnt, int64_t n_users, int64_t n_items, float* S,
+                               int64_t lds, int32_t lds_cap, void* workspace, size_t workspace_bytes, void* stream);
+int hiprec_knn_item_scores(const int64_t* b_ptr, const int64_t* b_idx, int64_t n_users, int64_t n_items, const float* S,
+                           int64_t lds, const int64_t* query_users, int64_t n_query, const int64_t* pair_ptr,
+                           const int64_t* pair_items, float* out_pick, int32_t topk, const int64_t* seen_ptr,
+                           const int64_t* seen_idx, int64_t* out_items, float* out_scores, int32_t lds_cap,
+                           void* workspace, size_t workspace_bytes, hiprec_stats* stats, void* stream);
+/* out_nb_ids / out_nb_sims [n_query, k] (both or neither NULL): the neighbours, best first */
+int hiprec_knn_user_scores(const int64_t* b_ptr, const int64_t* b_idx, const float* b_val, const int64_t* bt_ptr,
+                           const int64_t* bt_idx, const float* bt_val, const double* cu, int64_t n_users,
+                           int64_t n_items, int32_t k, const int64_t* query_users, int64_t n_query, int64_t* out_nb_ids,
+                           double* out_nb_sims, const int64_t* pair_ptr, const int64_t* pair_items, double* out_pick,
+                           int32_t topk, const int64_t* seen_ptr, const int64_t* seen_idx, int64_t* out_items,
+                           float* out_scores, int32_t lds_cap, void* workspace, size_t workspace_bytes,
+                           hiprec_stats* stats, void* stream);
+
 /* ================= PairwiseGMF, the CMN pre-training model (sibling models) ====
  * models/pairwise_gmf.py:28-46 parameters: user_memory [n_users, dim], item_memory [n_items, dim],
  * v = nn.Linear(dim, 1, bias=False).weight [1, dim].  The host keeps them in ONE flat buffer in that
