@@ -140,6 +140,20 @@ class UltraGcnParams(Structure):
                 ("negative_weight", c_float), ("gamma", c_float), ("lambda_", c_float)]
 
 
+MIXGCF_MAX_HOPS = 6
+MIXGCF_POOLS = {"concat": 0, "mean": 1, "sum": 2, "final": 3}
+
+
+class MixGcfPlan(Structure):
+    """hiprec_mixgcf_plan (include/hiprec.h)."""
+
+    _fields_ = [("a", Csr), ("at", Csr), ("n_users", c_int64), ("n_items", c_int64),
+                ("dim", c_int32), ("n_hops", c_int32), ("pool", c_int32), ("rns", c_int32), ("n_negs", c_int32),
+                ("k_neg", c_int32), ("l2", c_float), ("edge_scale", c_float), ("mess_scale", c_float), ("_pad", c_int32),
+                ("e0", c_void_p), ("g", c_void_p), ("zero_ws", c_void_p), ("zero_ws_floats", c_int64),
+                ("edge_keep", c_void_p * MIXGCF_MAX_HOPS), ("mess_keep", c_void_p * MIXGCF_MAX_HOPS)]
+
+
 class SasrecShape(Structure):
     """hiprec_sasrec_shape (include/hiprec.h)."""
 
@@ -430,6 +444,13 @@ SIGNATURES = {
          c_int32, c_int, c_double, c_double, c_double, c_double, _P, _P, _P, _P, c_int64, _P, c_size_t, _P, _P,
          c_size_t, _P],
     ),
+    "hiprec_mixgcf_plan_bytes": (c_size_t, []),
+    "hiprec_mixgcf_propagate": (c_int, [POINTER(MixGcfPlan), c_int32, _P]),
+    "hiprec_mixgcf_predict": (c_int, [POINTER(MixGcfPlan), _P, _P, c_int64, _P, _P, _P]),
+    "hiprec_mixgcf_grad": (
+        c_int,
+        [POINTER(MixGcfPlan), _P, _P, _P, c_int64, c_int64, _P, _P, c_float, _P, _P, c_size_t, _P],
+    ),
     "hiprec_sasrec_shape_bytes": (c_size_t, []),
     "hiprec_sasrec_param_floats": (c_int64, [POINTER(SasrecShape)]),
     "hiprec_sasrec_workspace_bytes": (c_size_t, [POINTER(SasrecShape), c_int64, c_int32]),
@@ -697,6 +718,8 @@ def load():
         raise RuntimeError("hiprec_tvbr_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vaecf_shape_bytes() != ctypes.sizeof(VaecfShape):
         raise RuntimeError("hiprec_vaecf_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_mixgcf_plan_bytes() != ctypes.sizeof(MixGcfPlan):
+        raise RuntimeError("hiprec_mixgcf_plan layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_ncf_plan_bytes() != ctypes.sizeof(NcfPlan):
         raise RuntimeError("hiprec_ncf_plan layout mismatch between _lib.py and libhiprec.so")
     _lib = _DeviceGuardedLib(lib)

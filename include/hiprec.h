@@ -1801,6 +1801,64 @@ int hiprec_vaecf_decode_at(const hiprec_vaecf_shape* shape, const float* w_flat,
                            const int64_t* rows, const int64_t* items, int64_t n, float* out, float* lse_out,
                            hiprec_stats* stats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ================= MixGCF (beta_rec/models/mixgcf.py) ================================================
+ * LightGCN propagation whose L + 1 hop tables all stay resident, a hop-mixing hard-negative sampler and a K-pair
+ * softplus loss (mixgcf.py:176-286).  Node rows are [users | items]; hop 0 is the flat parameter buffer itself, hops
+ * 1 .. L are L tables of [n_rows, dim] in `hops`.  The per-hop gradient tables mirror that: hop 0's is the flat gradient
+ * buffer g, hops 1 .. L are in `dhops`.  `hops` and `dhops` are ONE region (zero_ws: hops first, 2 * L * n_rows * dim
+ * floats) that a training step clears with one fill.
+ * Limits (checked, with an error text): n_hops <= HIPREC_MIXGCF_MAX_HOPS, dim <= 256, k_neg * (n_hops + 1) <= 64. */
+#define HIPREC_MIXGCF_MAX_HOPS 6
+#define HIPREC_MIXGCF_POOL_CONCAT 0
+#define HIPREC_MIXGCF_POOL_MEAN 1
+#define HIPREC_MIXGCF_POOL_SUM 2
+#define HIPREC_MIXGCF_POOL_FINAL 3
+typedef struct hiprec_mixgcf_plan {
+  hiprec_csr a;  /* forward graph */
+  hiprec_csr at; /* its transpose; at.eid maps its edges to the forward graph's (the edge keep bytes' order) */
+  int64_t n_users, n_items;
+  int32_t dim, n_hops; /* n_hops = context_hops = L */
+  int32_t pool;        /* HIPREC_MIXGCF_POOL_* */
+  int32_t rns;         /* != 0: ns == "rns": negative k is candidate column k, no mixing */
+  int32_t n_negs;      /* candidates per negative (ignored for rns) */
+  int32_t k_neg;       /* K */
+  float l2;            /* config["l2"] */
+  float edge_scale;    /* 1 / (1 - edge_dropout_rate): what a kept edge's value is multiplied by */
+  float mess_scale;    /* 1 / (1 - mess_dropout_rate) */
+  int32_t _pad;
+  float* e0;      /* [n_rows, dim] hop 0 = the parameters */
+  float* g;       /* [n_rows, dim] the flat gradient buffer (training) */
+  float* zero_ws; /* [2 * n_hops][n_rows][dim]: hop tables 1 .. L, then their gradient tables */
+  int64_t zero_ws_floats;
+  /* per hop l -> l + 1 of a training pass, NULL = no dropout there: one keep byte per forward edge (CSR order) and one
+   * per element of the hop's [n_rows, dim] output */
+  const uint8_t* edge_keep[HIPREC_MIXGCF_MAX_HOPS];
+  const uint8_t* mess_keep[HIPREC_MIXGCF_MAX_HOPS];
+} hiprec_mixgcf_plan;
+size_t hiprec_mixgcf_plan_bytes(void);
+
+/* ---- E_{l+1} = mess_keep_l (.) (A with edge_keep_l) E_l for l < n_hops (GraphConv.forward, mixgcf.py:46-67).
+ * train == 0 ignores the keep pointers (eval mode). */
+int hiprec_mixgcf_propagate(const hiprec_mixgcf_plan* plan, int32_t train, void* stream);
+
+/* ---- scores[k] = <pool(E[u_k]), pool(E[n_users + i_k])> on the hop tables a propagate call left (LightGCN.predict,
+ * mixgcf.py:135-157: no sigmoid).  An id out of range sets HIPREC_STATUS_ROW_OOB and yields NaN. */
+int hiprec_mixgcf_predict(const hiprec_mixgcf_plan* plan, const int64_t* users, const int64_t* items, int64_t n,
+                          float* scores, hiprec_stats* stats, void* stream);
+
+/* ---- zero_grad + forward + sampler + loss + backward of one MixGCF step: training propagation, then per batch row
+ * and k < k_neg the candidates neg[b * neg_stride + k * n_negs + j] (rns: the one candidate neg[b * neg_stride + k])
+ * are mixed with the positive at every hop, n' = seed * pos + (1 - seed) * cand with seeds[(b * k_neg + k) *
+ * (n_hops + 1) + hop] (NULL for rns), scored against the user and the best one per hop kept (ties: the lowest j;
+ * choice [batch, k_neg, n_hops + 1] int32 receives j, may be NULL);
+ * loss = mean_b log(1 + sum_k exp(s_neg_k - s_pos)) + l2 / 2 / batch * (|E0[u]|^2 + |E0[pos]|^2 + sum_k |n'_k,hop0|^2),
+ * the softplus shifted by its largest argument.  The gradient goes through the transposed hops into g (which must be
+ * zero on entry); the loss partials are left in scratch and the step counter advances.  A row with a user, positive
+ * or candidate id out of range is skipped whole and the status bits are set. */
+int hiprec_mixgcf_grad(const hiprec_mixgcf_plan* plan, const int64_t* users, const int64_t* pos, const int64_t* neg,
+                       int64_t neg_stride, int64_t batch, const float* seeds, int32_t* choice, float inv_batch,
+                       hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
