@@ -154,6 +154,22 @@ class MixGcfPlan(Structure):
                 ("edge_keep", c_void_p * MIXGCF_MAX_HOPS), ("mess_keep", c_void_p * MIXGCF_MAX_HOPS)]
 
 
+SGL_MAX_LAYERS = 6
+SGL_TILE_B = 32       # HIPREC_SGL_TILE_B / _N / MAX_SPLITS (include/hiprec.h), checked against the library at load
+SGL_TILE_N = 64
+SGL_MAX_SPLITS = 64
+
+
+class SglPlan(Structure):
+    """hiprec_sgl_plan (include/hiprec.h)."""
+
+    _fields_ = [("a", Csr), ("at", Csr), ("s", Csr), ("sub_val", (c_void_p * SGL_MAX_LAYERS) * 2),
+                ("n_users", c_int64), ("n_items", c_int64), ("dim", c_int32), ("n_layers", c_int32),
+                ("ssl_sides", c_int32), ("n_splits", c_int32), ("regs", c_float), ("ssl_reg", c_float),
+                ("ssl_temp", c_float), ("_pad", c_int32), ("e0", c_void_p), ("g", c_void_p), ("ws", c_void_p),
+                ("ws_floats", c_int64), ("batch_ws", c_void_p), ("batch_ws_floats", c_int64)]
+
+
 class SasrecShape(Structure):
     """hiprec_sasrec_shape (include/hiprec.h)."""
 
@@ -451,6 +467,15 @@ SIGNATURES = {
         c_int,
         [POINTER(MixGcfPlan), _P, _P, _P, c_int64, c_int64, _P, _P, c_float, _P, _P, c_size_t, _P],
     ),
+    "hiprec_sgl_plan_bytes": (c_size_t, []),
+    "hiprec_sgl_tile_b": (c_int32, []),
+    "hiprec_sgl_tile_n": (c_int32, []),
+    "hiprec_sgl_ws_floats": (c_int64, [c_int64, c_int32]),
+    "hiprec_sgl_batch_ws_floats": (c_int64, [c_int64, c_int32]),
+    "hiprec_sgl_sub_values": (c_int, [POINTER(Csr), _P, _P, _P, _P, c_int64, _P, _P, _P]),
+    "hiprec_sgl_propagate": (c_int, [POINTER(SglPlan), _P]),
+    "hiprec_sgl_predict": (c_int, [POINTER(SglPlan), _P, _P, c_int64, _P, _P, _P]),
+    "hiprec_sgl_grad": (c_int, [POINTER(SglPlan), _P, _P, _P, c_int64, _P, _P, _P, c_size_t, _P]),
     "hiprec_sasrec_shape_bytes": (c_size_t, []),
     "hiprec_sasrec_param_floats": (c_int64, [POINTER(SasrecShape)]),
     "hiprec_sasrec_workspace_bytes": (c_size_t, [POINTER(SasrecShape), c_int64, c_int32]),
@@ -720,6 +745,10 @@ def load():
         raise RuntimeError("hiprec_vaecf_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_mixgcf_plan_bytes() != ctypes.sizeof(MixGcfPlan):
         raise RuntimeError("hiprec_mixgcf_plan layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_sgl_plan_bytes() != ctypes.sizeof(SglPlan):
+        raise RuntimeError("hiprec_sgl_plan layout mismatch between _lib.py and libhiprec.so")
+    if (lib.hiprec_sgl_tile_b(), lib.hiprec_sgl_tile_n()) != (SGL_TILE_B, SGL_TILE_N):
+        raise RuntimeError("SGL tile sizes differ between _lib.py and libhiprec.so")
     if lib.hiprec_ncf_plan_bytes() != ctypes.sizeof(NcfPlan):
         raise RuntimeError("hiprec_ncf_plan layout mismatch between _lib.py and libhiprec.so")
     _lib = _DeviceGuardedLib(lib)

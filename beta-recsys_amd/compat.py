@@ -20,6 +20,7 @@ MIRRORS = {
     "beta_rec.models.lightgcn": "lightgcn",
     "beta_rec.models.ngcf": "ngcf",
     "beta_rec.models.mixgcf": "mixgcf",
+    "beta_rec.models.sgl": "sgl",
     "beta_rec.models.pairwise_gmf": "pairwise_gmf",
     "beta_rec.models.cmn": "cmn",
     "beta_rec.models.sasrec": "sasrec",

@@ -1859,6 +1859,65 @@ int hiprec_mixgcf_grad(const hiprec_mixgcf_plan* plan, const int64_t* users, con
                        int64_t neg_stride, int64_t batch, const float* seeds, int32_t* choice, float inv_batch,
                        hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ================= SGL (beta_rec/models/sgl.py) ======================================================
+ * Three LightGCN propagations (norm_adj and two augmented sub-graphs), BPR sum + regs on the main view, InfoNCE of the
+ * batch's view-1 rows against every view-2 row of their side (sgl.py:82-145, :188-226, :277-394).  Node rows are
+ * [users | items].  The sub-graphs share ONE structure, the symmetric bipartite CSR `s` of the training interactions
+ * (its own transpose); a view is a value array over its edges, zero where an edge was dropped (hiprec_sgl_sub_values),
+ * one per layer (the same pointer L times for node / edge dropout, L different ones for the random walk).
+ * Limits (checked, with an error text): dim 1 .. 256, n_layers 0 .. HIPREC_SGL_MAX_LAYERS. */
+#define HIPREC_SGL_MAX_LAYERS 6
+#define HIPREC_SGL_TILE_B 32     /* batch rows per InfoNCE tile */
+#define HIPREC_SGL_TILE_N 64     /* node rows per InfoNCE tile */
+#define HIPREC_SGL_MAX_SPLITS 64 /* most blocks the node dimension of the InfoNCE forward is split over */
+typedef struct hiprec_sgl_plan {
+  hiprec_csr a;  /* norm_adj */
+  hiprec_csr at; /* its transpose (backward of the main view) */
+  hiprec_csr s;  /* structure of the sub-graphs (val unused) */
+  const float* sub_val[2][HIPREC_SGL_MAX_LAYERS]; /* [view][layer]: values over s's edges */
+  int64_t n_users, n_items;
+  int32_t dim, n_layers;
+  int32_t ssl_sides; /* bit 0: user side, bit 1: item side; 0 = no sub-graph views at all (pretrain) */
+  int32_t n_splits;  /* blocks per batch tile of the InfoNCE forward; 0 = chosen from the shape */
+  float regs, ssl_reg, ssl_temp;
+  int32_t _pad;
+  float* e0; /* [n_rows, dim] the parameters */
+  float* g;  /* [n_rows, dim] the flat gradient buffer (training) */
+  float* ws; /* hiprec_sgl_ws_floats(n_rows, dim) floats: pooled main view | view 1 | view 2 | their three gradients |
+              * two hop buffers | the inverse row norms of view 1 and view 2 */
+  int64_t ws_floats;
+  float* batch_ws; /* hiprec_sgl_batch_ws_floats(batch, dim) floats (training) */
+  int64_t batch_ws_floats;
+} hiprec_sgl_plan;
+size_t hiprec_sgl_plan_bytes(void);
+int32_t hiprec_sgl_tile_b(void);
+int32_t hiprec_sgl_tile_n(void);
+int64_t hiprec_sgl_ws_floats(int64_t n_rows, int32_t dim);
+int64_t hiprec_sgl_batch_ws_floats(int64_t batch, int32_t dim);
+
+/* ---- values of one sub-graph (create_sgl_mat, sgl.py:464-527): deg[r] = kept edges of row r, val[e] = kept ?
+ * deg[r]^-1/2 * deg[c]^-1/2 : 0 (isolated rows give 0).  An edge is kept iff keep[edge_inter[e]] (edge_inter: the
+ * interaction number of every edge of s, so that both directions share a byte), or -- keep NULL -- iff
+ * keep_user[u] & keep_item[i] of its two ends (node dropout), or -- all three NULL -- always. */
+int hiprec_sgl_sub_values(const hiprec_csr* s, const int32_t* edge_inter, const uint8_t* keep, const uint8_t* keep_user,
+                          const uint8_t* keep_item, int64_t n_users, float* deg, float* val, void* stream);
+
+/* ---- the main view's hop sum E_0 + ... + E_L into the head of ws (eval: what predict and ranking read) */
+int hiprec_sgl_propagate(const hiprec_sgl_plan* plan, void* stream);
+
+/* ---- scores[k] = <mean-pooled user row, mean-pooled item row> on what hiprec_sgl_propagate left (sgl.py:396-405).
+ * An id out of range sets HIPREC_STATUS_ROW_OOB and yields NaN. */
+int hiprec_sgl_predict(const hiprec_sgl_plan* plan, const int64_t* users, const int64_t* items, int64_t n, float* scores,
+                       hiprec_stats* stats, void* stream);
+
+/* ---- zero_grad + forward + loss + backward of one SGL step.  loss = sum_b softplus(-(pos - neg)) + regs / 2 * (squares
+ * of the batch's hop-0 rows, once per occurrence) + ssl_reg * sum over sides and batch rows of
+ * (log sum_j exp((s_bj - 1) / temp) - (s_b,pos - 1) / temp).  parts[0..3] (device) receive bpr, emb, ssl and their sum;
+ * the sum also travels in scratch to the optimizer sweep.  g must be zero on entry.  A triple with an id out of range is
+ * skipped by the BPR stage and the status bits are set; the caller drops the step. */
+int hiprec_sgl_grad(const hiprec_sgl_plan* plan, const int64_t* users, const int64_t* pos, const int64_t* neg,
+                    int64_t batch, float* parts, hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
