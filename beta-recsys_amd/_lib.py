@@ -170,6 +170,23 @@ class SglPlan(Structure):
                 ("ws_floats", c_int64), ("batch_ws", c_void_p), ("batch_ws_floats", c_int64)]
 
 
+LCFN_MAX_LAYERS = 4
+LCFN_MAX_DIM = 128     # HIPREC_LCFN_* (include/hiprec.h); the tile and slot constants are checked against the library at load
+LCFN_MAX_FREQ = 256
+LCFN_MAX_WIDTH = 512
+LCFN_TILE_ROWS = 32
+LCFN_MAX_SLOTS = 256
+
+
+class LcfnPlan(Structure):
+    """hiprec_lcfn_plan (include/hiprec.h)."""
+
+    _fields_ = [("P", c_void_p), ("Q", c_void_p), ("n_users", c_int64), ("n_items", c_int64), ("f_user", c_int32),
+                ("f_item", c_int32), ("dim", c_int32), ("layer", c_int32), ("train_filters", c_int32), ("n_slots", c_int32),
+                ("lamda", c_float), ("_pad", c_int32), ("w", c_void_p), ("g", c_void_p), ("ws", c_void_p),
+                ("ws_floats", c_int64), ("batch_ws", c_void_p), ("batch_ws_floats", c_int64)]
+
+
 class SasrecShape(Structure):
     """hiprec_sasrec_shape (include/hiprec.h)."""
 
@@ -476,6 +493,15 @@ SIGNATURES = {
     "hiprec_sgl_propagate": (c_int, [POINTER(SglPlan), _P]),
     "hiprec_sgl_predict": (c_int, [POINTER(SglPlan), _P, _P, c_int64, _P, _P, _P]),
     "hiprec_sgl_grad": (c_int, [POINTER(SglPlan), _P, _P, _P, c_int64, _P, _P, _P, c_size_t, _P]),
+    "hiprec_lcfn_plan_bytes": (c_size_t, []),
+    "hiprec_lcfn_tile_rows": (c_int32, []),
+    "hiprec_lcfn_max_slots": (c_int32, []),
+    "hiprec_lcfn_loss_triples_per_block": (c_int32, []),
+    "hiprec_lcfn_ws_floats": (c_int64, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "hiprec_lcfn_batch_ws_floats": (c_int64, [c_int64]),
+    "hiprec_lcfn_propagate": (c_int, [POINTER(LcfnPlan), _P]),
+    "hiprec_lcfn_predict": (c_int, [POINTER(LcfnPlan), _P, _P, c_int64, _P, _P, _P]),
+    "hiprec_lcfn_grad": (c_int, [POINTER(LcfnPlan), _P, _P, _P, c_int64, _P, _P, _P, c_size_t, _P]),
     "hiprec_sasrec_shape_bytes": (c_size_t, []),
     "hiprec_sasrec_param_floats": (c_int64, [POINTER(SasrecShape)]),
     "hiprec_sasrec_workspace_bytes": (c_size_t, [POINTER(SasrecShape), c_int64, c_int32]),
@@ -749,6 +775,10 @@ def load():
         raise RuntimeError("hiprec_sgl_plan layout mismatch between _lib.py and libhiprec.so")
     if (lib.hiprec_sgl_tile_b(), lib.hiprec_sgl_tile_n()) != (SGL_TILE_B, SGL_TILE_N):
         raise RuntimeError("SGL tile sizes differ between _lib.py and libhiprec.so")
+    if lib.hiprec_lcfn_plan_bytes() != ctypes.sizeof(LcfnPlan):
+        raise RuntimeError("hiprec_lcfn_plan layout mismatch between _lib.py and libhiprec.so")
+    if (lib.hiprec_lcfn_tile_rows(), lib.hiprec_lcfn_max_slots()) != (LCFN_TILE_ROWS, LCFN_MAX_SLOTS):
+        raise RuntimeError("LCFN tile / slot constants differ between _lib.py and libhiprec.so")
     if lib.hiprec_ncf_plan_bytes() != ctypes.sizeof(NcfPlan):
         raise RuntimeError("hiprec_ncf_plan layout mismatch between _lib.py and libhiprec.so")
     _lib = _DeviceGuardedLib(lib)

@@ -301,3 +301,45 @@ class SessionLoader:
             padded[real] = self._flat[(self._start[order][:, None] + pos)[real]]
             yield (torch.from_numpy(np.ascontiguousarray(padded.T)), torch.from_numpy(self._labels[order].copy()),
                    lens.tolist())
+
+
+def hypergraph_laplacians(users, items, n_users, n_items):
+    """The user and item hypergraph Laplacians of deprecated_data_base.py:420-452 as scipy CSR matrices:
+    ``L_u = I - D_u^-1/2 H D_v^-1 H^T D_u^-1/2`` and the same with the roles swapped.  ``H`` is the binary incidence
+    matrix (a repeated pair is one entry); the degrees count every interaction, repeated ones included, and are clamped
+    from below as the reference clamps them (``max(sqrt(d), 1e-10)``, ``max(d, 1e-10)``)."""
+    import scipy.sparse as sp
+
+    users, items = np.asarray(users, dtype=np.int64).reshape(-1), np.asarray(items, dtype=np.int64).reshape(-1)
+    if users.size != items.size:
+        raise ValueError("users and items differ in length")
+    if users.size and (users.min() < 0 or users.max() >= n_users or items.min() < 0 or items.max() >= n_items):
+        raise ValueError("an interaction lies outside n_users x n_items")
+    epsilon = 0.1 ** 10
+    H = sp.csr_matrix((np.ones(users.size), (users, items)), shape=(n_users, n_items))
+    H.data[:] = 1.0                                       # the constructor summed repeated pairs
+    d_u = np.bincount(users, minlength=n_users).astype(np.float64)
+    d_v = np.bincount(items, minlength=n_items).astype(np.float64)
+    out = []
+    for Hs, d_node, d_edge in ((H, d_u, d_v), (H.T.tocsr(), d_v, d_u)):
+        D_n = sp.diags(1.0 / np.maximum(np.sqrt(d_node), epsilon))
+        D_e = sp.diags(1.0 / np.maximum(d_edge, epsilon))
+        out.append((sp.identity(Hs.shape[0]) - D_n @ Hs @ D_e @ Hs.T @ D_n).tocsr())
+    return out
+
+
+def graph_embeddings(users, items, n_users, n_items, cut_off):
+    """``[P, Q]`` for ``LCFN``: the ``int(cut_off * n)`` lowest-frequency eigenvectors of the two hypergraph Laplacians
+    (deprecated_data_base.py:411-467: ``eigsh(L, k, which="SM", tol=1e-5)``), as fp32 arrays ``[n_users, F_u]`` and
+    ``[n_items, F_i]`` with ascending eigenvalues.  One-off host preprocessing; an eigenvector's sign is arbitrary."""
+    from scipy.sparse.linalg import eigsh
+
+    out = []
+    for L, n in zip(hypergraph_laplacians(users, items, n_users, n_items), (n_users, n_items)):
+        k = int(cut_off * n)
+        if not 1 <= k < n:
+            raise ValueError(f"cut_off {cut_off} keeps {k} of {n} frequencies: 1 .. n - 1 are possible")
+        lam, vec = eigsh(L, k=k, which="SM", tol=0.1 ** 5)
+        order = np.argsort(lam, kind="stable")
+        out.append(np.ascontiguousarray(vec[:, order], dtype=np.float32))
+    return out

@@ -1918,6 +1918,64 @@ int hiprec_sgl_predict(const hiprec_sgl_plan* plan, const int64_t* users, const 
 int hiprec_sgl_grad(const hiprec_sgl_plan* plan, const int64_t* users, const int64_t* pos, const int64_t* neg,
                     int64_t batch, float* parts, hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ================= LCFN (beta_rec/models/lcfn.py) =====================================================
+ * Low-pass graph filters through two dense tall-and-skinny spectral bases P [n_users, f_user] and Q [n_items, f_item]
+ * (lcfn.py:55-87): per layer k = 1 .. L and per side  T_k = P^T X_{k-1},  M_k = (f_k (.) T_k) W_k,  X_k = sigmoid(P M_k);
+ * the all-embeddings row of a node is [X_0 | ... | X_L].  Loss (lcfn.py:171-205): -mean logsigmoid(pos - neg) of the
+ * all-rows' dot products + lamda * (the Frobenius norms of the three gathered hop-0 batch matrices + the norms of every
+ * filter and transformer).  diag(f), P diag(f) and anything [n, n] are never formed.
+ * Flat parameters w (and their gradient g): E_u [n_users, dim] | E_i [n_items, dim] | user filters [layer][f_user] |
+ * item filters [layer][f_item] | transformers [layer][dim][dim] (shared by both sides).
+ * Limits (checked, with an error text): dim 1 .. 128, f_user / f_item 1 .. 256, layer 1 .. HIPREC_LCFN_MAX_LAYERS,
+ * (layer + 1) * dim <= 512. */
+#define HIPREC_LCFN_MAX_LAYERS 4
+#define HIPREC_LCFN_MAX_DIM 128
+#define HIPREC_LCFN_MAX_FREQ 256
+#define HIPREC_LCFN_MAX_WIDTH 512 /* (layer + 1) * dim: the top-K path's widest row */
+#define HIPREC_LCFN_TILE_ROWS 32  /* rows of P per project / expand tile */
+#define HIPREC_LCFN_MAX_SLOTS 256 /* most partial slots (= project blocks) per side */
+#define HIPREC_LCFN_MID_ROWS 4    /* frequencies per block of the mid stage */
+typedef struct hiprec_lcfn_plan {
+  const float* P; /* [n_users, f_user] row-major */
+  const float* Q; /* [n_items, f_item] row-major */
+  int64_t n_users, n_items;
+  int32_t f_user, f_item, dim, layer;
+  int32_t train_filters; /* != 0: df, dW and the filters' / transformers' norm gradients go into g's tail */
+  int32_t n_slots;       /* partial slots per side of the project stage; 0 = HIPREC_LCFN_MAX_SLOTS (never more than tiles) */
+  float lamda;
+  int32_t _pad;
+  float* w; /* the flat parameters */
+  float* g; /* the flat gradient (training) */
+  float* ws; /* hiprec_lcfn_ws_floats(...) floats: all-embeddings of users | of items | their hop gradients | partial
+              * slots | T_k per layer | the padded mid results | dM | norms */
+  int64_t ws_floats;
+  float* batch_ws; /* hiprec_lcfn_batch_ws_floats(batch) floats (training) */
+  int64_t batch_ws_floats;
+} hiprec_lcfn_plan;
+size_t hiprec_lcfn_plan_bytes(void);
+int32_t hiprec_lcfn_tile_rows(void);
+int32_t hiprec_lcfn_max_slots(void);
+int32_t hiprec_lcfn_loss_triples_per_block(void);
+int64_t hiprec_lcfn_ws_floats(int64_t n_users, int64_t n_items, int32_t f_user, int32_t f_item, int32_t dim,
+                              int32_t layer, int32_t n_slots);
+int64_t hiprec_lcfn_batch_ws_floats(int64_t batch);
+
+/* ---- [X_0 | ... | X_L] of both sides into the head of ws (users' table, then items'), from the current w.  Partial
+ * sums are combined in a fixed order and nothing is accumulated with atomics: two runs give the same bits. */
+int hiprec_lcfn_propagate(const hiprec_lcfn_plan* plan, void* stream);
+
+/* ---- scores[k] = <all-row of users[k], all-row of items[k]> on what hiprec_lcfn_propagate left (lcfn.py:89-99).
+ * An id out of range sets HIPREC_STATUS_ROW_OOB and yields NaN. */
+int hiprec_lcfn_predict(const hiprec_lcfn_plan* plan, const int64_t* users, const int64_t* items, int64_t n, float* scores,
+                        hiprec_stats* stats, void* stream);
+
+/* ---- zero_grad + forward + loss + backward of one LCFN step.  parts[0..2] (device) receive the BPR mean, the
+ * regulariser and their sum; the sum also travels in scratch to the optimizer sweep.  g must be zero on entry.  A batch
+ * matrix whose norm is exactly 0 contributes gradient 0 (the reference writes NaN).  A triple with an id out of range is
+ * skipped and the status bits are set; the caller drops the step. */
+int hiprec_lcfn_grad(const hiprec_lcfn_plan* plan, const int64_t* users, const int64_t* pos, const int64_t* neg,
+                     int64_t batch, float* parts, hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
