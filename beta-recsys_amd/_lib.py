@@ -6,7 +6,7 @@ a symbol is absent, loading fails loudly with a RuntimeError naming the build co
 import ctypes
 import os
 from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64
-from ctypes import c_size_t, c_uint32, c_void_p
+from ctypes import c_size_t, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # HIPREC_LIB selects another build of the same sources, e.g. libhiprec_ieee.so (-DHIPREC_IEEE_DIV: ATen's
@@ -185,6 +185,22 @@ class LcfnPlan(Structure):
                 ("f_item", c_int32), ("dim", c_int32), ("layer", c_int32), ("train_filters", c_int32), ("n_slots", c_int32),
                 ("lamda", c_float), ("_pad", c_int32), ("w", c_void_p), ("g", c_void_p), ("ws", c_void_p),
                 ("ws_floats", c_int64), ("batch_ws", c_void_p), ("batch_ws_floats", c_int64)]
+
+
+SIMGCL_MAX_LAYERS = 4
+SIMGCL_MAX_DIM = 256   # HIPREC_SIMGCL_* (include/hiprec.h), checked against the library at load
+SIMGCL_TILE_B = 32
+SIMGCL_TILE_N = 64
+
+
+class SimgclPlan(Structure):
+    """hiprec_simgcl_plan (include/hiprec.h)."""
+
+    _fields_ = [("a", Csr), ("at", Csr), ("n_users", c_int64), ("n_items", c_int64), ("dim", c_int32),
+                ("n_layers", c_int32), ("user_view", c_int32), ("_pad", c_int32), ("eps", c_float), ("reg", c_float),
+                ("lambda_", c_float), ("cl_temp", c_float), ("noise_seed", c_uint64), ("noise", c_void_p),
+                ("e0", c_void_p), ("g", c_void_p), ("ws", c_void_p), ("ws_floats", c_int64), ("stamps", c_void_p),
+                ("batch_ws", c_void_p), ("batch_ws_floats", c_int64)]
 
 
 class SasrecShape(Structure):
@@ -502,6 +518,17 @@ SIGNATURES = {
     "hiprec_lcfn_propagate": (c_int, [POINTER(LcfnPlan), _P]),
     "hiprec_lcfn_predict": (c_int, [POINTER(LcfnPlan), _P, _P, c_int64, _P, _P, _P]),
     "hiprec_lcfn_grad": (c_int, [POINTER(LcfnPlan), _P, _P, _P, c_int64, _P, _P, _P, c_size_t, _P]),
+    "hiprec_simgcl_plan_bytes": (c_size_t, []),
+    "hiprec_simgcl_tile_b": (c_int32, []),
+    "hiprec_simgcl_tile_n": (c_int32, []),
+    "hiprec_simgcl_max_dim": (c_int32, []),
+    "hiprec_simgcl_max_layers": (c_int32, []),
+    "hiprec_simgcl_ws_floats": (c_int64, [c_int64, c_int32]),
+    "hiprec_simgcl_stamp_ints": (c_int64, [c_int64]),
+    "hiprec_simgcl_batch_ws_floats": (c_int64, [c_int64, c_int32]),
+    "hiprec_simgcl_noise": (c_int, [c_uint64, c_uint64, c_int32, c_int64, c_int32, _P, _P]),
+    "hiprec_simgcl_predict": (c_int, [POINTER(SimgclPlan), _P, _P, c_int64, _P, _P, _P]),
+    "hiprec_simgcl_grad": (c_int, [POINTER(SimgclPlan), _P, _P, _P, c_int64, _P, _P, _P, c_size_t, _P]),
     "hiprec_sasrec_shape_bytes": (c_size_t, []),
     "hiprec_sasrec_param_floats": (c_int64, [POINTER(SasrecShape)]),
     "hiprec_sasrec_workspace_bytes": (c_size_t, [POINTER(SasrecShape), c_int64, c_int32]),
@@ -779,6 +806,11 @@ def load():
         raise RuntimeError("hiprec_lcfn_plan layout mismatch between _lib.py and libhiprec.so")
     if (lib.hiprec_lcfn_tile_rows(), lib.hiprec_lcfn_max_slots()) != (LCFN_TILE_ROWS, LCFN_MAX_SLOTS):
         raise RuntimeError("LCFN tile / slot constants differ between _lib.py and libhiprec.so")
+    if lib.hiprec_simgcl_plan_bytes() != ctypes.sizeof(SimgclPlan):
+        raise RuntimeError("hiprec_simgcl_plan layout mismatch between _lib.py and libhiprec.so")
+    if (lib.hiprec_simgcl_tile_b(), lib.hiprec_simgcl_tile_n(), lib.hiprec_simgcl_max_dim(),
+            lib.hiprec_simgcl_max_layers()) != (SIMGCL_TILE_B, SIMGCL_TILE_N, SIMGCL_MAX_DIM, SIMGCL_MAX_LAYERS):
+        raise RuntimeError("SimGCL tile sizes / limits differ between _lib.py and libhiprec.so")
     if lib.hiprec_ncf_plan_bytes() != ctypes.sizeof(NcfPlan):
         raise RuntimeError("hiprec_ncf_plan layout mismatch between _lib.py and libhiprec.so")
     _lib = _DeviceGuardedLib(lib)

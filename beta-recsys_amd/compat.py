@@ -8,8 +8,8 @@ importing ``beta_rec.recommenders``.
 import sys
 
 # reference module name -> mirror module in this package.  ``beta_rec.models.torch_engine`` is NOT in
-# this table: the reference engines this package does not mirror (simgcl, buir and
-# the older ones) import ``ModelEngine`` from it and need the torch optimizer it builds
+# this table: the reference engines this package does not mirror (buir and the
+# older ones) import ``ModelEngine`` from it and need the torch optimizer it builds
 # (``self.optimizer.step()``); the mirrors import their own base class relatively.
 MIRRORS = {
     "beta_rec.models.mf": "mf",
@@ -22,6 +22,7 @@ MIRRORS = {
     "beta_rec.models.mixgcf": "mixgcf",
     "beta_rec.models.sgl": "sgl",
     "beta_rec.models.lcfn": "lcfn",
+    "beta_rec.models.simgcl": "simgcl",
     "beta_rec.models.pairwise_gmf": "pairwise_gmf",
     "beta_rec.models.cmn": "cmn",
     "beta_rec.models.sasrec": "sasrec",

@@ -1976,6 +1976,67 @@ int hiprec_lcfn_predict(const hiprec_lcfn_plan* plan, const int64_t* users, cons
 int hiprec_lcfn_grad(const hiprec_lcfn_plan* plan, const int64_t* users, const int64_t* pos, const int64_t* neg,
                      int64_t batch, float* parts, hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ================= SimGCL (beta_rec/models/simgcl.py) =================================================
+ * LightGCN propagation whose hops are perturbed, X_k = Y_k + sign(Y_k) * u / max(|u|, 1e-12) * eps with Y_k = A X_{k-1}
+ * and u uniform on [0, 1), mean-pooled over hops 1 .. L (hop 0 is not in the mean).  One step runs a clean view and two
+ * perturbed ones; loss = BPR sum of -log(1e-7 + sigmoid(pos - neg)) on the clean pool + reg * the three unsquared
+ * Frobenius norms of the batch's clean pooled rows + lambda * InfoNCE among the UNIQUE users (view 1 against view 1 or
+ * view 2, see user_view) and the unique positive items (view 1 against view 2).  sign() has no derivative, so all three
+ * views share one backward chain.  Node rows are [users | items].
+ * Limits (checked, with an error text): dim 1 .. HIPREC_SIMGCL_MAX_DIM, n_layers 1 .. HIPREC_SIMGCL_MAX_LAYERS. */
+#define HIPREC_SIMGCL_MAX_LAYERS 4
+#define HIPREC_SIMGCL_MAX_DIM 256
+#define HIPREC_SIMGCL_TILE_B 32 /* query rows per InfoNCE tile */
+#define HIPREC_SIMGCL_TILE_N 64 /* key rows per InfoNCE tile */
+typedef struct hiprec_simgcl_plan {
+  hiprec_csr a;  /* norm_adj */
+  hiprec_csr at; /* its transpose (the backward chain) */
+  int64_t n_users, n_items;
+  int32_t dim, n_layers;
+  int32_t user_view; /* 1: the user side contrasts view 1 with itself (simgcl.py:65), 2: with view 2 */
+  int32_t _pad;
+  float eps, reg, lambda, cl_temp;
+  uint64_t noise_seed;
+  const float* noise; /* [2, n_layers, n_rows, dim] uniforms to use, or NULL: drawn in registers from (noise_seed, the
+                       * workspace's step clock, view, hop, row, column) */
+  float* e0;          /* [n_rows, dim] the parameters */
+  float* g;           /* [n_rows, dim] the flat gradient buffer (training) */
+  float* ws;          /* hiprec_simgcl_ws_floats(n_rows, dim) floats: A E_0 | the three pools | two hop buffers | the ONE
+                       * gradient table G.  No noise is stored. */
+  int64_t ws_floats;
+  int32_t* stamps; /* hiprec_simgcl_stamp_ints(n_rows) ints, zero when first handed in: [0] the step clock, then one
+                    * stamp per node; never cleared */
+  float* batch_ws; /* hiprec_simgcl_batch_ws_floats(batch, dim) floats (training) */
+  int64_t batch_ws_floats;
+} hiprec_simgcl_plan;
+size_t hiprec_simgcl_plan_bytes(void);
+int32_t hiprec_simgcl_tile_b(void);
+int32_t hiprec_simgcl_tile_n(void);
+int32_t hiprec_simgcl_max_dim(void);
+int32_t hiprec_simgcl_max_layers(void);
+int64_t hiprec_simgcl_ws_floats(int64_t n_rows, int32_t dim);
+int64_t hiprec_simgcl_stamp_ints(int64_t n_rows);
+int64_t hiprec_simgcl_batch_ws_floats(int64_t batch, int32_t dim);
+
+/* ---- out[view][hop][row][col] = the uniform the device draw of (seed, step) uses there: a 24-bit fraction in [0, 1).
+ * For tests and draw_noise; training never stores it. */
+int hiprec_simgcl_noise(uint64_t seed, uint64_t step, int32_t n_layers, int64_t n_rows, int32_t dim, float* out,
+                        void* stream);
+
+/* ---- scores[k] = <user row, item row> of the RAW tables (simgcl.py:72-82: predict does not propagate).  An id out of
+ * range sets HIPREC_STATUS_ROW_OOB and yields NaN. */
+int hiprec_simgcl_predict(const hiprec_simgcl_plan* plan, const int64_t* users, const int64_t* items, int64_t n,
+                          float* scores, hiprec_stats* stats, void* stream);
+
+/* ---- zero_grad + forward + loss + backward of one SimGCL step.  parts[0..4] (device) receive bpr, reg, cl_user, cl_item
+ * (the two InfoNCE sums, not yet times lambda) and the loss; parts[5..7] the three batch norms.  The loss also travels in
+ * scratch to the optimizer sweep.  g must be zero on entry.  The unique ids, their counts and everything sized by them
+ * stay on the device.  A batch matrix whose norm is exactly 0 contributes gradient 0 (the reference writes NaN).  A
+ * triple with an id out of range is skipped and the status bits are set; the caller drops the step. */
+int hiprec_simgcl_grad(const hiprec_simgcl_plan* plan, const int64_t* users, const int64_t* pos, const int64_t* neg,
+                       int64_t batch, float* parts, hiprec_stats* stats, void* scratch, size_t scratch_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
