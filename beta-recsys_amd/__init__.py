@@ -16,6 +16,7 @@ from .mixgcf import MixGCF, MixGCFEngine  # noqa: F401
 from .sgl import SGL, SGLEngine  # noqa: F401
 from .lcfn import LCFN, LCFNEngine  # noqa: F401
 from .simgcl import SimGCL, SimGCLEngine  # noqa: F401
+from .buir import BUIR_NB, BUIREngine  # noqa: F401
 from .pairwise_gmf import PairwiseGMF, PairwiseGMFEngine  # noqa: F401
 from .cmn import CollaborativeMemoryNetwork, cmnEngine  # noqa: F401
 from .sasrec import SASRec, SASRecEngine  # noqa: F401

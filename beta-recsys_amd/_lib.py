@@ -203,6 +203,21 @@ class SimgclPlan(Structure):
                 ("batch_ws", c_void_p), ("batch_ws_floats", c_int64)]
 
 
+BUIR_MAX_LAYERS = 4
+BUIR_MAX_DIM = 256     # HIPREC_BUIR_* (include/hiprec.h), checked against the library at load
+BUIR_TILE_B = 32
+
+
+class BuirPlan(Structure):
+    """hiprec_buir_plan (include/hiprec.h)."""
+
+    _fields_ = [("a", Csr), ("at", Csr), ("n_users", c_int64), ("n_items", c_int64), ("dim", c_int32),
+                ("n_layers", c_int32), ("apply_pending", c_int32), ("_pad", c_int32), ("momentum", c_float),
+                ("one_minus_momentum", c_float), ("online", c_void_p), ("target", c_void_p), ("w", c_void_p),
+                ("b", c_void_p), ("g_online", c_void_p), ("g_w", c_void_p), ("g_b", c_void_p), ("ws", c_void_p),
+                ("ws_floats", c_int64), ("batch_ws", c_void_p), ("batch_ws_floats", c_int64)]
+
+
 class SasrecShape(Structure):
     """hiprec_sasrec_shape (include/hiprec.h)."""
 
@@ -529,6 +544,16 @@ SIGNATURES = {
     "hiprec_simgcl_noise": (c_int, [c_uint64, c_uint64, c_int32, c_int64, c_int32, _P, _P]),
     "hiprec_simgcl_predict": (c_int, [POINTER(SimgclPlan), _P, _P, c_int64, _P, _P, _P]),
     "hiprec_simgcl_grad": (c_int, [POINTER(SimgclPlan), _P, _P, _P, c_int64, _P, _P, _P, c_size_t, _P]),
+    "hiprec_buir_plan_bytes": (c_size_t, []),
+    "hiprec_buir_tile_b": (c_int32, []),
+    "hiprec_buir_max_dim": (c_int32, []),
+    "hiprec_buir_max_layers": (c_int32, []),
+    "hiprec_buir_ws_floats": (c_int64, [c_int64, c_int32]),
+    "hiprec_buir_batch_ws_floats": (c_int64, [c_int64, c_int32]),
+    "hiprec_buir_pool": (c_int, [POINTER(BuirPlan), _P, _P, _P, _P]),
+    "hiprec_buir_grad": (c_int, [POINTER(BuirPlan), _P, _P, _P, c_int64, _P, _P, c_size_t, _P]),
+    "hiprec_buir_ema": (c_int, [POINTER(BuirPlan), _P]),
+    "hiprec_buir_predict": (c_int, [POINTER(BuirPlan), _P, _P, c_int64, _P, _P, _P]),
     "hiprec_sasrec_shape_bytes": (c_size_t, []),
     "hiprec_sasrec_param_floats": (c_int64, [POINTER(SasrecShape)]),
     "hiprec_sasrec_workspace_bytes": (c_size_t, [POINTER(SasrecShape), c_int64, c_int32]),
@@ -811,6 +836,11 @@ def load():
     if (lib.hiprec_simgcl_tile_b(), lib.hiprec_simgcl_tile_n(), lib.hiprec_simgcl_max_dim(),
             lib.hiprec_simgcl_max_layers()) != (SIMGCL_TILE_B, SIMGCL_TILE_N, SIMGCL_MAX_DIM, SIMGCL_MAX_LAYERS):
         raise RuntimeError("SimGCL tile sizes / limits differ between _lib.py and libhiprec.so")
+    if lib.hiprec_buir_plan_bytes() != ctypes.sizeof(BuirPlan):
+        raise RuntimeError("hiprec_buir_plan layout mismatch between _lib.py and libhiprec.so")
+    if (lib.hiprec_buir_tile_b(), lib.hiprec_buir_max_dim(), lib.hiprec_buir_max_layers()) != (
+            BUIR_TILE_B, BUIR_MAX_DIM, BUIR_MAX_LAYERS):
+        raise RuntimeError("BUIR tile size / limits differ between _lib.py and libhiprec.so")
     if lib.hiprec_ncf_plan_bytes() != ctypes.sizeof(NcfPlan):
         raise RuntimeError("hiprec_ncf_plan layout mismatch between _lib.py and libhiprec.so")
     _lib = _DeviceGuardedLib(lib)

@@ -8,9 +8,9 @@ importing ``beta_rec.recommenders``.
 import sys
 
 # reference module name -> mirror module in this package.  ``beta_rec.models.torch_engine`` is NOT in
-# this table: the reference engines this package does not mirror (buir and the
-# older ones) import ``ModelEngine`` from it and need the torch optimizer it builds
-# (``self.optimizer.step()``); the mirrors import their own base class relatively.
+# this table: every model of the reference has a mirror here, but an engine of a caller's own that
+# imports ``ModelEngine`` from it needs the torch optimizer it builds (``self.optimizer.step()``);
+# the mirrors import their own base class relatively.
 MIRRORS = {
     "beta_rec.models.mf": "mf",
     "beta_rec.models.ncf": "ncf",
@@ -23,6 +23,7 @@ MIRRORS = {
     "beta_rec.models.sgl": "sgl",
     "beta_rec.models.lcfn": "lcfn",
     "beta_rec.models.simgcl": "simgcl",
+    "beta_rec.models.buir": "buir",
     "beta_rec.models.pairwise_gmf": "pairwise_gmf",
     "beta_rec.models.cmn": "cmn",
     "beta_rec.models.sasrec": "sasrec",

@@ -2037,6 +2037,70 @@ int hiprec_simgcl_grad(const hiprec_simgcl_plan* plan, const int64_t* users, con
                        int64_t batch, float* parts, hiprec_stats* stats, void* scratch, size_t scratch_bytes,
                        void* stream);
 
+/* ================= BUIR (beta_rec/models/buir.py) =====================================================
+ * Two LightGCN encoders over norm_adj, an online one that trains and a target one that does not, and one shared
+ * predictor y = x W^T + b.  pool(E_0) = mean(E_0, A E_0, .., A^L E_0): hop 0 IS in the mean.  Per batch row (u, i):
+ * loss = (2 - 2 n(y_u).n(t_i)) + (2 - 2 n(y_i).n(t_u)), n(v) = v / max(|v|, 1e-12), x from the online pool, t from the
+ * target pool; the batch MEAN.  Gradients reach the online tables (through the pool), W and b; none reaches the target.
+ * The reference never moves its target, so the pooled target table is a constant kept in the workspace: a step runs
+ * L SpMMs forward and L backward.  With update_target the raw target follows T <- m T + (1 - m) O after every optimizer
+ * step (hiprec_buir_ema) and, the pool being linear, the pooled target follows at the next step's forward from the
+ * pooled online rows (apply_pending).  Node rows are [users | items].
+ * Limits (checked, with an error text): dim 1 .. HIPREC_BUIR_MAX_DIM, n_layers 1 .. HIPREC_BUIR_MAX_LAYERS, batch <=
+ * 2048 * HIPREC_BUIR_TILE_B. */
+#define HIPREC_BUIR_MAX_LAYERS 4
+#define HIPREC_BUIR_MAX_DIM 256
+#define HIPREC_BUIR_TILE_B 32 /* batch rows per block of the fused kernel: 2 * TILE_B stacked user / item rows */
+typedef struct hiprec_buir_plan {
+  hiprec_csr a;  /* norm_adj */
+  hiprec_csr at; /* its transpose (the backward chain) */
+  int64_t n_users, n_items;
+  int32_t dim, n_layers;
+  int32_t apply_pending; /* grad only: the pooled target is one moving-average update behind; apply it in the forward */
+  int32_t _pad;
+  float momentum;           /* (float)m */
+  float one_minus_momentum; /* (float)(1.0 - m), the difference taken in double as python takes it */
+  const float* online; /* [n_rows, dim] the online tables */
+  float* target;       /* [n_rows, dim] the raw target tables (hiprec_buir_ema writes them) */
+  const float* w;      /* [dim, dim] predictor.weight */
+  const float* b;      /* [dim] predictor.bias */
+  float* g_online;     /* [n_rows, dim] gradient slots (training; zero on entry) */
+  float* g_w;          /* [dim, dim] */
+  float* g_b;          /* [dim] */
+  float* ws;           /* hiprec_buir_ws_floats(n_rows, dim) floats: pooled online | pooled target | the gradient table |
+                        * two hop buffers */
+  int64_t ws_floats;
+  float* batch_ws; /* hiprec_buir_batch_ws_floats(batch, dim) floats: the blocks' dW / db partial sums (training) */
+  int64_t batch_ws_floats;
+} hiprec_buir_plan;
+size_t hiprec_buir_plan_bytes(void);
+int32_t hiprec_buir_tile_b(void);
+int32_t hiprec_buir_max_dim(void);
+int32_t hiprec_buir_max_layers(void);
+int64_t hiprec_buir_ws_floats(int64_t n_rows, int32_t dim);
+int64_t hiprec_buir_batch_ws_floats(int64_t batch, int32_t dim);
+
+/* ---- out = pool(table) ([n_rows, dim] each; the hop buffers of plan->ws are used).  out may be a slot of plan->ws: the
+ * pooled target, slot 1 (plan->ws + n_rows * dim), is (re)built with table = plan->target.  proj (optional, [n_rows,
+ * dim], outside plan->ws): also proj = out W^T + b, what ranking_factors needs. */
+int hiprec_buir_pool(const hiprec_buir_plan* plan, const float* table, float* out, float* proj, void* stream);
+
+/* ---- zero_grad + forward + loss + backward of one BUIR step: the loss travels in scratch to the optimizer sweep; the
+ * gradient slots must be zero on entry.  neg is accepted and never read (buir.py:226-228).  A row with an id out of range
+ * is skipped and the status bits are set; the caller drops the step. */
+int hiprec_buir_grad(const hiprec_buir_plan* plan, const int64_t* users, const int64_t* pos, const int64_t* neg,
+                     int64_t batch, hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- target <- momentum * target + (1 - momentum) * online on the raw tables, rounded as the reference's
+ * _update_target rounds (two products, one sum). */
+int hiprec_buir_ema(const hiprec_buir_plan* plan, void* stream);
+
+/* ---- scores[k] = p(P[u]).P[U + i] + P[u].p(P[U + i]) with P = pool(online) (buir.py:79-100).  Propagates (L SpMMs) and
+ * overwrites the pooled-online slot and a hop buffer of plan->ws.  An id out of range sets HIPREC_STATUS_ROW_OOB and
+ * yields NaN. */
+int hiprec_buir_predict(const hiprec_buir_plan* plan, const int64_t* users, const int64_t* items, int64_t n,
+                        float* scores, hiprec_stats* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
