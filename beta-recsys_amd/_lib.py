@@ -648,6 +648,12 @@ SIGNATURES = {
         [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int32, _P, c_int64, _P, _P, _P, _P, _P, c_int32, _P, _P, _P, _P,
          c_int32, _P, c_size_t, _P, _P],
     ),
+    "hiprec_als_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
+    "hiprec_als_gram": (c_int, [_P, c_int64, c_int32, c_float, _P, _P, _P, c_size_t, _P]),
+    "hiprec_als_solve_rows": (
+        c_int, [_P, _P, _P, _P, c_int64, _P, c_int64, c_int32, _P, c_float, _P, c_int32, _P, _P, _P]),
+    "hiprec_als_loss": (
+        c_int, [_P, _P, _P, c_int64, _P, _P, c_int64, c_int32, _P, c_float, c_float, _P, c_size_t, _P, _P, _P]),
     "hiprec_stage_epoch": (c_int, [_P, _P, _P, c_int32, _P, c_int64, c_int64, _P, _P, _P, _P]),
     "hiprec_stage_epoch_shuffled": (c_int, [_P, _P, _P, c_int32, ctypes.c_uint64, c_int64, c_int64, _P, _P, _P, _P]),
     "hiprec_mf_bce_epoch": (

@@ -2101,6 +2101,47 @@ int hiprec_buir_ema(const hiprec_buir_plan* plan, void* stream);
 int hiprec_buir_predict(const hiprec_buir_plan* plan, const int64_t* users, const int64_t* items, int64_t n,
                         float* scores, hiprec_stats* stats, void* stream);
 
+/* ================= Implicit ALS (WRMF, Hu, Koren and Volinsky 2008): exact alternating least squares (csrc/als.hip) ====
+ * No counterpart in the reference.  r_ui = multiplicity of the pair (u, i) in the training frame, handed over as the
+ * CSRs of knn: ptr device int64 [rows + 1], idx device int64 ascending and unique per row, val device fp32.
+ *
+ *   p_ui = [r_ui > 0]      c_ui = 1 + alpha r_ui
+ *   L(X, Y) = sum over ALL (u, i) of c_ui (p_ui - x_u . y_i)^2 + reg (|X|_F^2 + |Y|_F^2)
+ *   half-sweep, G = Y^T Y:   A_u = G + reg I + sum_{i in N(u)} alpha r_ui y_i y_i^T
+ *                            b_u =             sum_{i in N(u)} (1 + alpha r_ui) y_i          x_u = A_u^{-1} b_u
+ *   (the item half-sweep: the transposed CSR, the tables swapped)
+ *
+ * 1 <= dim <= HIPREC_ALS_MAX_DIM; the kernels are instantiated for dim padded to a multiple of 16.  No float atomics
+ * anywhere: every sum has one owner and a fixed order.  Nothing is allocated; all entry points validate before any HIP
+ * call.  workspace: hiprec_als_workspace_bytes(n_users, n_items, dim) bytes, (size_t)-1 for a bad shape; it holds the
+ * Gram stage's per-block slots and the loss stage's per-row partials. */
+#define HIPREC_ALS_MAX_DIM 128
+#define HIPREC_ALS_CHUNK 64       /* neighbours staged into LDS at a time (a multiple of the MFMA's K = 4) */
+#define HIPREC_ALS_GRAM_SLOTS 128 /* most blocks (= partial slots) of the Gram stage */
+#define HIPREC_ALS_MAX_BLOCKS 1024
+size_t hiprec_als_workspace_bytes(int64_t n_users, int64_t n_items, int32_t dim);
+/* G = F^T F and G_reg = G + reg I ([dim, dim] each, both symmetric bit for bit) of F [n, dim] on the fp32 MFMA: block b
+ * reduces the 64-row tiles b, b + slots, ... into its slot; a second stage adds the slots in slot order. */
+int hiprec_als_gram(const float* F, int64_t n, int32_t dim, float reg, float* G, float* G_reg, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* One half-sweep: out[row] = A_row^{-1} b_row for every row of the CSR (n_rows rows over n_other columns), `other` the
+ * [n_other, dim] table of the other side, G_reg = other^T other + reg I.  out [n_rows, dim]: the side's own table, or a
+ * caller's buffer (fold-in).  order: device int64 [n_rows], a permutation of the rows -- position p is solved by block
+ * p mod grid, so the longest rows go first; NULL = 0, 1, 2 ....  blocks: 0 = the library's choice, else the grid
+ * (<= HIPREC_ALS_MAX_BLOCKS).  A row's bits depend on `other`, G_reg and the row's list only.  A row without entries is
+ * written as zeros.  A pivot that is not finite or <= 0 leaves the row untouched and adds one to *failed (device
+ * int32; the caller clears it).  An idx outside [0, n_other) or an order entry outside [0, n_rows) sets
+ * HIPREC_STATUS_ITEM_OOB / HIPREC_STATUS_ROW_OOB and is skipped. */
+int hiprec_als_solve_rows(const int64_t* ptr, const int64_t* idx, const float* val, const int64_t* order,
+                          int64_t n_rows, const float* other, int64_t n_other, int32_t dim, const float* G_reg,
+                          float alpha, float* out, int32_t blocks, int32_t* failed, hiprec_stats* stats, void* stream);
+/* out[0] = L(X, Y), out[1] = its regulariser reg (|X|_F^2 + trace G) (device fp64 [2]) without forming a score outside
+ * the frame:  L = sum_u x_u^T G x_u + sum_{(u,i) in frame} [c_ui (1 - s)^2 - s^2] + reg (|X|_F^2 + trace G),
+ * s = x_u . y_i, G = Y^T Y as hiprec_als_gram left it.  Per-row partials in fp64, folded in a fixed order. */
+int hiprec_als_loss(const int64_t* ptr, const int64_t* idx, const float* val, int64_t n_users, const float* X,
+                    const float* Y, int64_t n_items, int32_t dim, const float* G, float alpha, float reg,
+                    void* workspace, size_t workspace_bytes, double* out, hiprec_stats* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
