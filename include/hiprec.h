@@ -2142,6 +2142,44 @@ int hiprec_als_loss(const int64_t* ptr, const int64_t* idx, const float* val, in
                     const float* Y, int64_t n_items, int32_t dim, const float* G, float alpha, float reg,
                     void* workspace, size_t workspace_bytes, double* out, hiprec_stats* stats, void* stream);
 
+/* ================= EASE (Steck 2019): the closed-form item autoencoder by dense Cholesky (csrc/ease.hip) ===============
+ * No counterpart in the reference.  X = the BINARY [n_users, n_items] matrix of the training frame (a pair counts once
+ * however often it occurs), handed over as the two CSRs of knn (ptr device int64 [rows + 1], idx device int64 ascending
+ * and unique per row; the values are not read).
+ *
+ *   G = X^T X + reg I        P = G^-1        B[i, j] = -P[i, j] / P[j, j]  (i != j),   B[j, j] = 0
+ *
+ * All matrices are [n_items, n_items] fp32, row-major, leading dimension n_items.  No float atomics: the same input
+ * gives the same bits on every run.  Nothing is allocated; every entry point validates before any HIP call.
+ * Limits: 1 <= n_users < HIPREC_EASE_MAX_USERS (an fp32 count stays exact), 1 <= n_items <= HIPREC_EASE_MAX_ITEMS.
+ * workspace: hiprec_ease_workspace_bytes(n_users, n_items) bytes, (size_t)-1 for a bad shape: one more [n_items, n_items]
+ * fp32 matrix, which also holds the Gram stage's integer accumulators when a row of them does not fit LDS. */
+#define HIPREC_STATUS_NOT_SPD 256u      /* EASE: a pivot of the Cholesky factorisation was not positive and finite */
+#define HIPREC_EASE_PANEL 64            /* columns of a Cholesky panel = K of every trailing update */
+#define HIPREC_EASE_TILE 64             /* rows and columns of the tile a block updates (four waves, 32 x 32 each) */
+#define HIPREC_EASE_MFMA 16             /* v_mfma_f32_16x16x4_f32 */
+#define HIPREC_EASE_LDS_CAP 7168        /* accumulator entries the Gram stage keeps in LDS (as HIPREC_KNN_LDS_CAP) */
+#define HIPREC_EASE_MAX_USERS 16777216  /* 2^24, exclusive */
+#define HIPREC_EASE_MAX_ITEMS 1048576
+size_t hiprec_ease_workspace_bytes(int64_t n_users, int64_t n_items);
+/* G = X^T X + reg I: bt = the item-major CSR (rows = items, idx = users), b = the user-major one.  Off the diagonal G
+ * holds the integer co-occurrence counts exactly; on it float(count) + reg.  lds_cap: 0 = HIPREC_EASE_LDS_CAP (its
+ * maximum); the result does not depend on it.  An id out of range sets HIPREC_STATUS_USER_OOB / _ITEM_OOB and is
+ * skipped. */
+int hiprec_ease_gram(const int64_t* bt_ptr, const int64_t* bt_idx, const int64_t* b_ptr, const int64_t* b_idx,
+                     int64_t n_users, int64_t n_items, float reg, float* G, int32_t lds_cap, void* workspace,
+                     size_t workspace_bytes, hiprec_stats* stats, void* stream);
+/* A (symmetric positive definite; only its lower triangle is read) -> the LOWER triangle of A^-1, in place, by a blocked
+ * Cholesky factorisation with the forward substitution L^-1 carried along in `workspace` (n * n * 4 bytes, not A) and
+ * A^-1 = L^-T L^-1.  Four launches per panel of HIPREC_EASE_PANEL columns and three more.  A pivot that is not positive
+ * and finite sets HIPREC_STATUS_NOT_SPD and every later launch of the call does nothing: A is then neither the input nor
+ * the inverse.  The caller clears the status word before the call. */
+int hiprec_ease_invert(float* A, int64_t n, void* workspace, size_t workspace_bytes, hiprec_stats* stats, void* stream);
+/* B from the lower triangle of P = G^-1 (both triangles of B written, its diagonal +0); P's upper triangle is filled
+ * from its lower one.  B must not be P (it may be the workspace of hiprec_ease_invert).  Does nothing while
+ * HIPREC_STATUS_NOT_SPD is set. */
+int hiprec_ease_finish(float* P, int64_t n, float* B, hiprec_stats* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
