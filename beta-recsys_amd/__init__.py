@@ -30,6 +30,7 @@ from .ultragcn import UltraGCN, UltraGCNEngine, get_ii_constraint_mat  # noqa: F
 from .knn import ItemKNN, ItemKNNEngine, UserKNN, UserKNNEngine  # noqa: F401
 from .als import ALS, ALSEngine  # noqa: F401
 from .ease import EASE, EASEEngine  # noqa: F401
+from .slim import SLIM, SLIMEngine  # noqa: F401
 from . import eval  # noqa: F401,A004  (evaluate / predict / rank_metrics)
 from . import data  # noqa: F401  (device-side loaders / negative sampling)
 from .recommend import recommend  # noqa: F401  (top-K over the whole catalogue, csrc/topk.hip)

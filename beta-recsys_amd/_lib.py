@@ -25,6 +25,7 @@ STATUS_LAZY_TABLE = 32
 STATUS_TABLE_FULL = 64
 STATUS_TIME_OOB = 128
 STATUS_NOT_SPD = 256
+STATUS_NOT_FINITE = 512
 
 
 class MfTables(Structure):
@@ -660,6 +661,9 @@ SIGNATURES = {
         c_int, [_P, _P, _P, _P, c_int64, c_int64, c_float, _P, c_int32, _P, c_size_t, _P, _P]),
     "hiprec_ease_invert": (c_int, [_P, c_int64, _P, c_size_t, _P, _P]),
     "hiprec_ease_finish": (c_int, [_P, c_int64, _P, _P, _P]),
+    "hiprec_slim_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "hiprec_slim_fit": (
+        c_int, [_P, c_int64, c_float, c_int32, c_float, c_int32, _P, _P, c_int32, _P, c_size_t, _P, _P]),
     "hiprec_stage_epoch": (c_int, [_P, _P, _P, c_int32, _P, c_int64, c_int64, _P, _P, _P, _P]),
     "hiprec_stage_epoch_shuffled": (c_int, [_P, _P, _P, c_int32, ctypes.c_uint64, c_int64, c_int64, _P, _P, _P, _P]),
     "hiprec_mf_bce_epoch": (

@@ -44,13 +44,82 @@ def _check_bytes(n_items, max_sim_bytes):
     return need
 
 
-class EASE(_KNNBase):
+class _ItemWeightsBase(_KNNBase):
+    """What the models with a dense ``[n_items, n_items]`` fp32 ``item_weights`` matrix share (EASE, SLIM): scoring and
+    ranking through ItemKNN's stage with that matrix, ``recommend_for`` and the checkpoint."""
+
+    SCORE_DTYPE = torch.float32
+
+    # ---- scoring ----------------------------------------------------------------------------------------------------
+    def _score_call(self, csr, n_rows, query, pair_ptr, pair_items, out_pick, topk, seen, out_items, out_scores):
+        if self.item_weights is None:
+            raise RuntimeError(f"{type(self).__name__}: call prepare_model(data) first")
+        dev = query.device
+        lib = _lib.load()
+        need = lib.hiprec_knn_workspace_bytes(OP_ITEM_SCORES, n_rows, self.n_items, query.numel(), self.lds_cap)
+        ws = torch.empty(max(need // 8, 1), dtype=torch.int64, device=dev)
+        _lib.check(lib.hiprec_knn_item_scores(
+            _lib.ptr(csr[0]), _lib.ptr(_idx(csr[1])), n_rows, self.n_items, _lib.ptr(self.item_weights), self.n_items,
+            _lib.ptr(query), query.numel(), _lib.ptr(pair_ptr), _lib.ptr(pair_items), _lib.ptr(out_pick), topk,
+            _lib.ptr(seen[0]) if seen else None, _lib.ptr(seen[1]) if seen else None, _lib.ptr(out_items),
+            _lib.ptr(out_scores), self.lds_cap, _lib.ptr(ws), need, _lib.ptr(self._stats), _lib.stream_ptr(dev)))
+
+    def _scores(self, query, pair_ptr, pair_items, out_pick, topk, seen, out_items, out_scores):
+        self._score_call(self._b, self.n_users, query, pair_ptr, pair_items, out_pick, topk, seen, out_items, out_scores)
+
+    def recommend_for(self, ptr, idx, k, exclude=True):
+        """Top-``k`` for users outside the frame: row ``r`` of the CSR ``(ptr[n + 1], idx)`` is a user's item list (any
+        order; an item listed twice counts once).  ``(items[n, k] int64, scores[n, k] float32)``, best first, ties to
+        the lower id; ``exclude=True`` never returns an item of the user's own list.  A user with an empty list gets
+        ``-1`` / ``-inf`` throughout (there is nothing to score from); an id outside ``[0, n_items)`` raises IndexError."""
+        if self.item_weights is None:
+            raise RuntimeError(f"{type(self).__name__}: call prepare_model(data) first")
+        dev = self.item_weights.device
+        k = int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k must be in 1..{MAX_K}, got {k}")
+        ptr_t, idx_t = index_tensor(ptr, dev).reshape(-1), index_tensor(idx, dev).reshape(-1)
+        n = ptr_t.numel() - 1
+        if n < 0 or (n >= 0 and (int(ptr_t[0]) != 0 or int(ptr_t[-1]) != idx_t.numel()
+                                 or (n > 0 and bool((ptr_t[1:] < ptr_t[:-1]).any())))):
+            raise ValueError("ptr must rise from 0 to len(idx)")
+        out_items = torch.full((n, k), -1, dtype=torch.int64, device=dev)
+        out_scores = torch.full((n, k), float("-inf"), dtype=torch.float32, device=dev)
+        if n == 0 or idx_t.numel() == 0:
+            return out_items, out_scores
+        lengths = ptr_t[1:] - ptr_t[:-1]
+        rows = torch.repeat_interleave(torch.arange(n, device=dev), lengths)
+        csr = build_interaction_csr(rows, idx_t, n, self.n_items)[:2]      # IndexError for an id out of range
+        if self._stats is None:
+            self._stats = _new_stats(dev)
+        query = torch.arange(n, dtype=torch.int64, device=dev)
+        self._score_call(csr, n, query, None, None, None, k, csr if exclude else None, out_items, out_scores)
+        self._raise_status((out_items, out_scores))
+        empty = (lengths == 0).unsqueeze(1)
+        return out_items.masked_fill_(empty, -1), out_scores.masked_fill_(empty, float("-inf"))
+
+    # ---- checkpoint: the weights are the model ----------------------------------------------------------------------
+    def state_dict(self, *args, **kwargs):
+        sd = super().state_dict(*args, **kwargs)
+        if self.item_weights is not None:
+            sd["item_weights"] = self.item_weights
+        return sd
+
+    def load_state_dict(self, state_dict, strict=True):
+        B = state_dict.get("item_weights")
+        if B is None:
+            self.item_weights = None
+            return
+        if tuple(B.shape) != (self.n_items, self.n_items):
+            raise ValueError(f"item_weights is {tuple(B.shape)}, this model has n_items={self.n_items}")
+        self.item_weights = B.to(device=self._device(), dtype=torch.float32).contiguous().clone()
+
+
+class EASE(_ItemWeightsBase):
     """Config keys: ``n_users``, ``n_items``, ``reg`` (lambda > 0, default 500.0), ``device_str``, ``max_sim_bytes``
     (default 4 GiB; bounds ``G`` plus the workspace, ``2 * n_items^2 * 4`` bytes).  ``lds_cap`` moves the Gram stage's
     accumulator between LDS and the workspace (the result does not depend on it) and ``keep_inverse=True`` keeps
     ``P = G^-1`` as ``self.inverse`` -- both for the tests."""
-
-    SCORE_DTYPE = torch.float32
 
     def __init__(self, config):
         super().__init__(dict(config, neighbourhood_size=0))
@@ -142,70 +211,6 @@ class EASE(_KNNBase):
         self._raise_not_spd()
         self.item_weights = B
         self.inverse = G if self.keep_inverse else None
-
-    # ---- scoring ----------------------------------------------------------------------------------------------------
-    def _score_call(self, csr, n_rows, query, pair_ptr, pair_items, out_pick, topk, seen, out_items, out_scores):
-        if self.item_weights is None:
-            raise RuntimeError("EASE: call prepare_model(data) first")
-        dev = query.device
-        lib = _lib.load()
-        need = lib.hiprec_knn_workspace_bytes(OP_ITEM_SCORES, n_rows, self.n_items, query.numel(), self.lds_cap)
-        ws = torch.empty(max(need // 8, 1), dtype=torch.int64, device=dev)
-        _lib.check(lib.hiprec_knn_item_scores(
-            _lib.ptr(csr[0]), _lib.ptr(_idx(csr[1])), n_rows, self.n_items, _lib.ptr(self.item_weights), self.n_items,
-            _lib.ptr(query), query.numel(), _lib.ptr(pair_ptr), _lib.ptr(pair_items), _lib.ptr(out_pick), topk,
-            _lib.ptr(seen[0]) if seen else None, _lib.ptr(seen[1]) if seen else None, _lib.ptr(out_items),
-            _lib.ptr(out_scores), self.lds_cap, _lib.ptr(ws), need, _lib.ptr(self._stats), _lib.stream_ptr(dev)))
-
-    def _scores(self, query, pair_ptr, pair_items, out_pick, topk, seen, out_items, out_scores):
-        self._score_call(self._b, self.n_users, query, pair_ptr, pair_items, out_pick, topk, seen, out_items, out_scores)
-
-    def recommend_for(self, ptr, idx, k, exclude=True):
-        """Top-``k`` for users outside the frame: row ``r`` of the CSR ``(ptr[n + 1], idx)`` is a user's item list (any
-        order; an item listed twice counts once).  ``(items[n, k] int64, scores[n, k] float32)``, best first, ties to
-        the lower id; ``exclude=True`` never returns an item of the user's own list.  A user with an empty list gets
-        ``-1`` / ``-inf`` throughout (there is nothing to score from); an id outside ``[0, n_items)`` raises IndexError."""
-        if self.item_weights is None:
-            raise RuntimeError("EASE: call prepare_model(data) first")
-        dev = self.item_weights.device
-        k = int(k)
-        if not 1 <= k <= MAX_K:
-            raise ValueError(f"k must be in 1..{MAX_K}, got {k}")
-        ptr_t, idx_t = index_tensor(ptr, dev).reshape(-1), index_tensor(idx, dev).reshape(-1)
-        n = ptr_t.numel() - 1
-        if n < 0 or (n >= 0 and (int(ptr_t[0]) != 0 or int(ptr_t[-1]) != idx_t.numel()
-                                 or (n > 0 and bool((ptr_t[1:] < ptr_t[:-1]).any())))):
-            raise ValueError("ptr must rise from 0 to len(idx)")
-        out_items = torch.full((n, k), -1, dtype=torch.int64, device=dev)
-        out_scores = torch.full((n, k), float("-inf"), dtype=torch.float32, device=dev)
-        if n == 0 or idx_t.numel() == 0:
-            return out_items, out_scores
-        lengths = ptr_t[1:] - ptr_t[:-1]
-        rows = torch.repeat_interleave(torch.arange(n, device=dev), lengths)
-        csr = build_interaction_csr(rows, idx_t, n, self.n_items)[:2]      # IndexError for an id out of range
-        if self._stats is None:
-            self._stats = _new_stats(dev)
-        query = torch.arange(n, dtype=torch.int64, device=dev)
-        self._score_call(csr, n, query, None, None, None, k, csr if exclude else None, out_items, out_scores)
-        self._raise_status((out_items, out_scores))
-        empty = (lengths == 0).unsqueeze(1)
-        return out_items.masked_fill_(empty, -1), out_scores.masked_fill_(empty, float("-inf"))
-
-    # ---- checkpoint: B is the model ---------------------------------------------------------------------------------
-    def state_dict(self, *args, **kwargs):
-        sd = super().state_dict(*args, **kwargs)
-        if self.item_weights is not None:
-            sd["item_weights"] = self.item_weights
-        return sd
-
-    def load_state_dict(self, state_dict, strict=True):
-        B = state_dict.get("item_weights")
-        if B is None:
-            self.item_weights = None
-            return
-        if tuple(B.shape) != (self.n_items, self.n_items):
-            raise ValueError(f"item_weights is {tuple(B.shape)}, this model has n_items={self.n_items}")
-        self.item_weights = B.to(device=self._device(), dtype=torch.float32).contiguous().clone()
 
 
 class EASEEngine(_KNNEngine):

@@ -2180,6 +2180,34 @@ int hiprec_ease_invert(float* A, int64_t n, void* workspace, size_t workspace_by
  * HIPREC_STATUS_NOT_SPD is set. */
 int hiprec_ease_finish(float* P, int64_t n, float* B, hiprec_stats* stats, void* stream);
 
+/* ================= SLIM (Ning and Karypis 2011): the sparse linear item model by coordinate descent (csrc/slim.hip) =====
+ * No counterpart in the reference.  A = X^T X + l2 I is hiprec_ease_gram's matrix with reg = l2 ([n, n] fp32, symmetric,
+ * integer counts off the diagonal); G = A off the diagonal.  For every item j the column w = W[:, j] minimises
+ *
+ *   1/2 w^T A w - G[:, j]^T w + l1 sum |w_k|      subject to w_j = 0 and, with positive_only = 1, w >= 0
+ *
+ * by cyclic coordinate descent from w = 0.  A sweep visits k = 0 .. n-1 in ascending order, skips k = j and keeps
+ * q = A w up to date; with b = G[k, j]:
+ *   positive   g = (q_k - b) + l1,              w_new = max(0, w_k - g / A_kk)
+ *   signed     r = b - (q_k - A_kk w_k),        w_new = sign(r) max(0, |r| - l1) / A_kk
+ *   d = w_new - w_k; when d != 0, q += d A[:, k] and w_k = w_new.
+ * A column stops after the first sweep whose largest |d| is <= tol (tol = 0: a sweep that changes nothing), or after
+ * max_sweeps sweeps.  sweeps_out[j] = the number of sweeps of column j, NEGATED when the column stopped without meeting
+ * tol.  Every operation is a single correctly rounded fp32 operation in a fixed order (no fma, no atomics, no
+ * communication between workgroups): W is a function of A and the parameters alone, whatever lds_cap says.
+ * W: [n, n] fp32 row-major, every entry written, the diagonal +0; W must not be A.  A value that is not finite (NaN or
+ * inf in A, a zero on its diagonal) ends its column at once and sets HIPREC_STATUS_NOT_FINITE; nothing faults or hangs.
+ * lds_cap: 0 = HIPREC_SLIM_LDS_CAP (its maximum); above it w and q live in the workspace.
+ * workspace: hiprec_slim_workspace_bytes(n, lds_cap) bytes, (size_t)-1 for a bad shape. */
+#define HIPREC_STATUS_NOT_FINITE 512u   /* SLIM: a coordinate step was NaN or infinite */
+#define HIPREC_SLIM_CHUNK 64            /* candidates evaluated at once: the lanes of a wave */
+#define HIPREC_SLIM_LDS_CAP 8192        /* items whose w and q (2 x 4 bytes each) a block keeps in LDS: 64 KiB */
+#define HIPREC_SLIM_MAX_SWEEPS 1000000
+size_t hiprec_slim_workspace_bytes(int64_t n, int32_t lds_cap);
+int hiprec_slim_fit(const float* A, int64_t n, float l1, int32_t positive_only, float tol, int32_t max_sweeps, float* W,
+                    int32_t* sweeps_out, int32_t lds_cap, void* workspace, size_t workspace_bytes, hiprec_stats* stats,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
