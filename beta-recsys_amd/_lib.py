@@ -233,6 +233,13 @@ class TisasrecShape(Structure):
                 ("time_span", c_int32), ("n_blocks", c_int32), ("_pad", c_int32)]
 
 
+class Bert4recShape(Structure):
+    """hiprec_bert4rec_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_items", c_int64), ("dim", c_int32), ("heads", c_int32), ("maxlen", c_int32), ("n_blocks", c_int32),
+                ("ffn_dim", c_int32), ("_pad", c_int32)]
+
+
 class NarmShape(Structure):
     """hiprec_narm_shape (include/hiprec.h)."""
 
@@ -572,6 +579,15 @@ SIGNATURES = {
         [POINTER(TisasrecShape), _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_float, _P, c_float, _P, _P, _P, c_size_t,
          _P, c_size_t, _P],
     ),
+    "hiprec_bert4rec_shape_bytes": (c_size_t, []),
+    "hiprec_bert4rec_param_floats": (c_int64, [POINTER(Bert4recShape)]),
+    "hiprec_bert4rec_workspace_bytes": (c_size_t, [POINTER(Bert4recShape), c_int64, c_int32]),
+    "hiprec_bert4rec_grad": (
+        c_int,
+        [POINTER(Bert4recShape), _P, _P, _P, c_int64, _P, _P, c_int64, c_int32, _P, c_float, _P, _P, _P, c_size_t, _P,
+         c_size_t, _P],
+    ),
+    "hiprec_bert4rec_head": (c_int, [POINTER(Bert4recShape), _P, _P, c_int64, _P, _P, c_size_t, _P]),
     "hiprec_narm_shape_bytes": (c_size_t, []),
     "hiprec_narm_param_floats": (c_int64, [POINTER(NarmShape)]),
     "hiprec_narm_workspace_bytes": (c_size_t, [POINTER(NarmShape), c_int64, c_int32]),
@@ -829,6 +845,8 @@ def load():
         raise RuntimeError("hiprec_sasrec_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_tisasrec_shape_bytes() != ctypes.sizeof(TisasrecShape):
         raise RuntimeError("hiprec_tisasrec_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_bert4rec_shape_bytes() != ctypes.sizeof(Bert4recShape):
+        raise RuntimeError("hiprec_bert4rec_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_narm_shape_bytes() != ctypes.sizeof(NarmShape):
         raise RuntimeError("hiprec_narm_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vbcar_shape_bytes() != ctypes.sizeof(VbcarShape):

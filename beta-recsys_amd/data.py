@@ -196,6 +196,56 @@ class SequenceSampler:
         """The reference's sampler owns worker processes; this one owns nothing."""
 
 
+class ClozeSampler:
+    """Host-side batches for BERT4Rec's cloze task: a uniformly random user with at least one item; the last ``maxlen``
+    items, left-padded with 0; every real position replaced by ``[MASK]`` (``n_items + 1``) independently with
+    probability ``mask_prob``; a sequence in which none was drawn gets its LAST position masked, so every sequence
+    trains and the last-item case the model is queried with is seen.  ``labels`` hold the original item at the masked
+    positions and 0 elsewhere.
+
+    ``user_train``: dict user id -> list of item ids (1-based, in time order).  ``next_batch()`` returns
+    ``(users [B], seq [B, maxlen], labels [B, maxlen])`` int64 arrays -- what ``BERT4RecEngine.train_an_epoch`` asks
+    for.  The same ``seed`` gives the same batches.  ``last_forced [B]`` tells which sequences of the last batch had
+    their mask forced.  ``n_users`` is kept for the signature of the other samplers."""
+
+    def __init__(self, user_train, n_users, n_items, batch_size, maxlen, mask_prob=0.2, seed=0):
+        self.n_users, self.n_items = int(n_users), int(n_items)
+        self.batch_size, self.maxlen = int(batch_size), int(maxlen)
+        self.mask_prob = float(mask_prob)
+        self.mask_id = self.n_items + 1
+        if not 0.0 < self.mask_prob < 1.0:
+            raise ValueError("mask_prob must be in (0, 1)")
+        if self.batch_size < 1 or self.maxlen < 1:
+            raise ValueError("batch_size and maxlen must be >= 1")
+        self.users = np.array(sorted(u for u, items in user_train.items() if len(items) >= 1), dtype=np.int64)
+        if self.users.size == 0:
+            raise ValueError("no user has an item")
+        # every user's last maxlen items as one left-padded table: a batch is a row gather
+        self.table = np.zeros((self.users.size, self.maxlen), dtype=np.int64)
+        for r, u in enumerate(self.users):
+            items = np.asarray(user_train[u], dtype=np.int64)
+            if items.min() < 1 or items.max() > self.n_items:
+                raise IndexError(f"user {u} holds an item outside [1, {self.n_items}]")
+            n = min(self.maxlen, items.size)
+            self.table[r, self.maxlen - n:] = items[-n:]
+        self.rng = np.random.default_rng(seed)
+        self.last_forced = None
+
+    def next_batch(self):
+        rows = self.rng.integers(0, self.users.size, self.batch_size)
+        hist = self.table[rows]
+        real = hist != 0
+        masked = real & (self.rng.random(hist.shape) < self.mask_prob)
+        self.last_forced = ~masked.any(1)
+        masked[self.last_forced, -1] = True        # left-padded: the last position is always real
+        seq = np.where(masked, self.mask_id, hist)
+        labels = np.where(masked, hist, 0)
+        return self.users[rows], seq, labels
+
+    def close(self):
+        """Owns nothing."""
+
+
 def instance_vae_loader(users, items, n_users, n_items):
     """``(user_indices, matrix)`` as base_data.py:513-532 hands them to ``VAECFEngine.train_an_epoch``: the ids of the
     users that occur, ascending, and the ``[n_users, n_items]`` scipy CSR matrix of the interactions (one per distinct

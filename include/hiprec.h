@@ -1602,6 +1602,56 @@ int hiprec_narm_grad(const hiprec_narm_shape* shape, const float* w_flat, float*
                      hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ================= BERT4Rec (Sun et al., CIKM 2019; no counterpart in the reference) ==================
+ * Ids: 0 = padding, 1 .. n_items = items, n_items + 1 = [MASK].  The parameters live in ONE flat buffer in state_dict()
+ * order: item_emb [n_items + 2, dim] (row 0 = padding, last row = [MASK]), pos_emb [maxlen, dim], emb_layernorm.{weight,
+ * bias}; attention_layers.{k}.{in_proj_weight [3 dim, dim], in_proj_bias, out_proj.weight, out_proj.bias};
+ * attention_layernorms.{k}.{weight, bias}; forward_layers.{k}.{fc1.weight [ffn_dim, dim], fc1.bias, fc2.weight
+ * [dim, ffn_dim], fc2.bias}; forward_layernorms.{k}.{weight, bias}, each group for k = 0 .. n_blocks - 1;
+ * head.dense.{weight [dim, dim], bias}, head.layernorm.{weight, bias}, out_bias [n_items + 1] (entry 0 is never read).
+ * dim <= 128, dim / heads in {16, 32, 64}, maxlen <= 256, ffn_dim in 1 .. 512.
+ * Forward on seq [batch, seq_len]: x = drop(LN(E[seq] + P[t])); per block q, k, v = in_proj(x), softmax over ALL keys
+ * with seq != 0 (a query with no such key gets a zero attention output), x = LN(x + drop(out_proj(.))),
+ * x = LN(x + drop(fc2(gelu(fc1(x))))) -- post-LN, exact (erf) GELU, LayerNorm eps 1e-8. */
+typedef struct hiprec_bert4rec_shape {
+  int64_t n_items;
+  int32_t dim;
+  int32_t heads;
+  int32_t maxlen;
+  int32_t n_blocks;
+  int32_t ffn_dim;
+  int32_t _pad;
+} hiprec_bert4rec_shape;
+size_t hiprec_bert4rec_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_bert4rec_param_floats(const hiprec_bert4rec_shape* shape);
+/* bytes of device workspace a hiprec_bert4rec_grad call on `batch` sequences of `seq_len` positions needs (0 for an
+ * unsupported shape).  It does not depend on n_items: no score of a (labelled row, item) pair is kept in memory. */
+size_t hiprec_bert4rec_workspace_bytes(const hiprec_bert4rec_shape* shape, int64_t batch, int32_t seq_len);
+
+/* ---- zero_grad + forward + loss + backward of BERT4RecEngine.train_single_batch on seq [batch, seq_len] and the
+ * labelled positions as a compact list: lab_pos [n_lab] (row b * seq_len + t, ascending, unique) and lab_item [n_lab]
+ * (the original item, in 1 .. n_items).  For each h = LN(gelu(head.dense(x[lab_pos]))): logit_j = <h, E[j]> +
+ * out_bias[j] over j = 1 .. n_items; loss = mean of logsumexp_j(logit) - logit_label.  n_lab == 0: loss 0, no gradient.
+ * Accumulates into the dense gradient g_flat (zero on entry, laid out like w_flat), leaves the loss partials in scratch
+ * and advances the step counter.  Every gradient except the rows of item_emb that occur in seq (row atomics) is the same
+ * bit for bit from run to run.
+ * keep: NULL (no dropout) or a HOST array of 1 + 3 n_blocks device pointers to keep bytes: embedding
+ * [batch * seq_len, dim]; per block the attention probabilities [batch * heads, seq_len, seq_len], dropout1 and dropout2
+ * [batch * seq_len, dim]; a kept value is multiplied by keep_scale.
+ * g_flat == NULL: forward only in eval mode (keep and the labels ignored, no loss): feats_out [batch * seq_len, dim]
+ * receives the last block's output; scratch may then be NULL.
+ * An id outside [0, n_items + 1] in seq, a label outside [1, n_items] or a position outside the batch sets
+ * HIPREC_STATUS_ITEM_OOB and is skipped. */
+int hiprec_bert4rec_grad(const hiprec_bert4rec_shape* shape, const float* w_flat, float* g_flat, const int64_t* seq,
+                         int64_t n_lab, const int64_t* lab_pos, const int64_t* lab_item, int64_t batch, int32_t seq_len,
+                         const uint8_t* const* keep, float keep_scale, float* feats_out, hiprec_stats* stats,
+                         void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
+/* out [n, dim] = head.layernorm(gelu(head.dense(rows [n, dim]))); tmp: 2 * roundup4(n * dim) + 2 * roundup4(n) floats */
+int hiprec_bert4rec_head(const hiprec_bert4rec_shape* shape, const float* w_flat, const float* rows, int64_t n,
+                         float* out, float* tmp, size_t tmp_floats, void* stream);
+
 /* ================= VBCAR (beta_rec/models/vbcar.py) ================================================
  * The parameters live in ONE flat buffer in state_dict() order: user_emb [n_users, emb_dim], item_emb [n_items, emb_dim],
  * fc_u_1_mu.weight [late_dim, fea_u], .bias [late_dim], fc_u_2_mu.weight [2 emb_dim, late_dim], .bias [2 emb_dim], then
