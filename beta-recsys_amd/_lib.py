@@ -246,6 +246,13 @@ class NarmShape(Structure):
     _fields_ = [("n_items", c_int64), ("emb_dim", c_int32), ("hidden", c_int32), ("n_layers", c_int32), ("_pad", c_int32)]
 
 
+class CaserShape(Structure):
+    """hiprec_caser_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_users", c_int64), ("n_items", c_int64), ("dim", c_int32), ("L", c_int32), ("T", c_int32),
+                ("N", c_int32), ("n_v", c_int32), ("n_h", c_int32), ("ac_conv", c_int32), ("ac_fc", c_int32)]
+
+
 class VbcarShape(Structure):
     """hiprec_vbcar_shape (include/hiprec.h)."""
 
@@ -596,6 +603,15 @@ SIGNATURES = {
         [POINTER(NarmShape), _P, _P, _P, _P, _P, c_int64, c_int32, _P, c_float, c_float, _P, _P, _P, c_size_t, _P,
          c_size_t, _P],
     ),
+    "hiprec_caser_shape_bytes": (c_size_t, []),
+    "hiprec_caser_param_floats": (c_int64, [POINTER(CaserShape)]),
+    "hiprec_caser_workspace_bytes": (c_size_t, [POINTER(CaserShape), c_int64]),
+    "hiprec_caser_grad": (
+        c_int,
+        [POINTER(CaserShape), _P, _P, _P, _P, _P, _P, c_int64, _P, c_float, c_float, _P, _P, _P, c_size_t, _P, c_size_t,
+         _P],
+    ),
+    "hiprec_caser_score": (c_int, [POINTER(CaserShape), _P, _P, _P, c_int64, c_int32, _P, _P, _P]),
     "hiprec_vbcar_shape_bytes": (c_size_t, []),
     "hiprec_vbcar_param_floats": (c_int64, [POINTER(VbcarShape)]),
     "hiprec_vbcar_workspace_bytes": (c_size_t, [POINTER(VbcarShape), c_int64, c_int32]),
@@ -849,6 +865,8 @@ def load():
         raise RuntimeError("hiprec_bert4rec_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_narm_shape_bytes() != ctypes.sizeof(NarmShape):
         raise RuntimeError("hiprec_narm_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_caser_shape_bytes() != ctypes.sizeof(CaserShape):
+        raise RuntimeError("hiprec_caser_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vbcar_shape_bytes() != ctypes.sizeof(VbcarShape):
         raise RuntimeError("hiprec_vbcar_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_tvbr_shape_bytes() != ctypes.sizeof(TvbrShape):

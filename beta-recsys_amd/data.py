@@ -246,6 +246,93 @@ class ClozeSampler:
         """Owns nothing."""
 
 
+class WindowSampler:
+    """Host-side batches for Caser: every stride-1 window of ``L + T`` consecutive items of every user, the first ``L``
+    as the input sequence and the last ``T`` as the targets.  A history shorter than ``L + T`` becomes ONE window,
+    left-padded with 0 (its targets are all real); a user with ``len <= T`` has no input and is left out.
+
+    ``user_train``: dict user id -> list of item ids (1-based, in time order).  An epoch is one pass: ``len(sampler)``
+    batches of ``(users [B], seq [B, L], pos [B, T], neg [B, neg_samples])`` int64 arrays in a fresh random order, the
+    last batch ragged.  The negatives are uniform over ``1 .. n_items`` outside the user's own set and are redrawn every
+    epoch.  The same ``seed`` gives the same epochs."""
+
+    def __init__(self, user_train, n_users, n_items, batch_size, L, T, neg_samples, seed=0):
+        self.n_users, self.n_items = int(n_users), int(n_items)
+        self.batch_size, self.L, self.T, self.neg_samples = int(batch_size), int(L), int(T), int(neg_samples)
+        if min(self.batch_size, self.L, self.T, self.neg_samples) < 1:
+            raise ValueError("batch_size, L, T and neg_samples must be >= 1")
+        users, windows, keys = [], [], []
+        width = self.L + self.T
+        for u in sorted(user_train):
+            items = np.asarray(user_train[u], dtype=np.int64).reshape(-1)
+            if not 0 <= int(u) < self.n_users:
+                raise IndexError(f"user {u} outside [0, {self.n_users})")
+            if items.size and (items.min() < 1 or items.max() > self.n_items):
+                raise IndexError(f"user {u} holds an item outside [1, {self.n_items}]")
+            if items.size <= self.T:
+                continue
+            own = np.unique(items)
+            if own.size >= self.n_items:
+                raise ValueError(f"user {u} has interacted with every item: no negative can be drawn")
+            keys.append(int(u) * (self.n_items + 1) + own)
+            if items.size < width:
+                w = np.zeros((1, width), dtype=np.int64)
+                w[0, width - items.size:] = items
+            else:
+                w = np.lib.stride_tricks.sliding_window_view(items, width)
+            users.append(np.full(w.shape[0], int(u), dtype=np.int64))
+            windows.append(w)
+        if not windows:
+            raise ValueError(f"no user has more than T = {self.T} items")
+        self.users = np.concatenate(users)
+        self.windows = np.ascontiguousarray(np.concatenate(windows))
+        self._keys = np.concatenate(keys)       # sorted: users ascending, each user's items ascending
+        self.rng = np.random.default_rng(seed)
+
+    def __len__(self):
+        return (self.users.size + self.batch_size - 1) // self.batch_size
+
+    def _draw_negatives(self):
+        n = self.users.size
+        neg = self.rng.integers(1, self.n_items + 1, (n, self.neg_samples))
+        base = self.users[:, None] * (self.n_items + 1)
+        while True:
+            key = base + neg
+            at = np.minimum(np.searchsorted(self._keys, key), self._keys.size - 1)
+            hit = self._keys[at] == key
+            if not hit.any():
+                return neg
+            neg[hit] = self.rng.integers(1, self.n_items + 1, int(hit.sum()))
+
+    def __iter__(self):
+        order = self.rng.permutation(self.users.size)
+        neg = self._draw_negatives()
+        for s in range(0, order.size, self.batch_size):
+            idx = order[s:s + self.batch_size]
+            w = self.windows[idx]
+            yield self.users[idx], w[:, :self.L], w[:, self.L:], neg[idx]
+
+    def close(self):
+        """Owns nothing."""
+
+
+def last_window(user_train, L):
+    """The query sequences of Caser: the last ``L`` items of every history, left-padded with 0.  ``user_train``: a dict
+    user id -> item list, which gives ``(users [n], seq [n, L])`` with the users ascending, or a list of item lists,
+    which gives ``seq [n, L]`` in the list's order.  int64 arrays."""
+    L = int(L)
+    if L < 1:
+        raise ValueError("L must be >= 1")
+    by_user = isinstance(user_train, dict)
+    users = sorted(user_train) if by_user else None
+    hists = [user_train[u] for u in users] if by_user else list(user_train)
+    seq = np.zeros((len(hists), L), dtype=np.int64)
+    for r, h in enumerate(hists):
+        items = np.asarray(h, dtype=np.int64).reshape(-1)[-L:]
+        seq[r, L - items.size:] = items
+    return (np.asarray(users, dtype=np.int64), seq) if by_user else seq
+
+
 def instance_vae_loader(users, items, n_users, n_items):
     """``(user_indices, matrix)`` as base_data.py:513-532 hands them to ``VAECFEngine.train_an_epoch``: the ids of the
     users that occur, ascending, and the ``[n_users, n_items]`` scipy CSR matrix of the interactions (one per distinct

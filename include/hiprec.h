@@ -1652,6 +1652,64 @@ int hiprec_bert4rec_grad(const hiprec_bert4rec_shape* shape, const float* w_flat
 int hiprec_bert4rec_head(const hiprec_bert4rec_shape* shape, const float* w_flat, const float* rows, int64_t n,
                          float* out, float* tmp, size_t tmp_floats, void* stream);
 
+/* ================= Caser (Tang and Wang, WSDM 2018; no counterpart in the reference) ==================
+ * Ids: items are 1 .. n_items and 0 is padding; users are 0 .. n_users - 1.  The parameters live in ONE flat buffer in
+ * state_dict() order: user_embeddings.weight [n_users, dim], item_embeddings.weight [n_items + 1, dim] (row 0 is zero
+ * and stays zero), conv_v.weight [n_v, 1, L, 1], conv_v.bias [n_v]; conv_h.{i}.weight [n_h, 1, i + 1, dim],
+ * conv_h.{i}.bias [n_h] for i = 0 .. L - 1; fc1.weight [dim, n_v dim + n_h L], fc1.bias [dim]; W2.weight
+ * [n_items + 1, 2 dim]; b2.weight [n_items + 1, 1].
+ * Limits: dim in 1 .. 128 (any value), L in 1 .. 10, n_v in 1 .. 16, n_h in 1 .. 64, T in 1 .. 16, N in 1 .. 64.
+ * Forward on seq [batch, L], users [batch]: E = item_embeddings[seq] [batch, L, dim];
+ *   out_v[b, c, j] = conv_v.bias[c] + sum_l conv_v.weight[c, l] E[b, l, j], flattened [n_v, dim] row-major, NO activation;
+ *   for each height h = 1 .. L and t = 0 .. L - h:
+ *     pre[b, f, t] = conv_h.{h-1}.bias[f] + sum_{i<h} <conv_h.{h-1}.weight[f, i, :], E[b, t + i, :]>,
+ *     out_h[b, (h - 1) n_h + f] = max_t ac_conv(pre[b, f, t]) (the backward follows the arg-max; a tie goes to the lowest t);
+ *   o = drop([out_v | out_h]), z = ac_fc(fc1(o)), x = [z | user_embeddings[users]] [batch, 2 dim];
+ *   score[b, item] = <x[b], W2[item]> + b2[item].
+ * Loss on pos [batch, T], neg [batch, N]: mean over the real pos of softplus(-score) + mean over the real neg of
+ * softplus(score).  An entry 0 is "no item": skipped and not counted in its mean; a mean over nothing is 0.
+ * Weight decay: g += l2 * w for EVERY parameter element after the backward (Adam's weight_decay); it is not part of the
+ * reported loss. */
+#define HIPREC_CASER_AC_RELU 0
+#define HIPREC_CASER_AC_TANH 1
+#define HIPREC_CASER_AC_SIGM 2
+#define HIPREC_CASER_AC_IDEN 3
+typedef struct hiprec_caser_shape {
+  int64_t n_users;
+  int64_t n_items;   /* without the padding id: the item tables have n_items + 1 rows */
+  int32_t dim;
+  int32_t L;
+  int32_t T;
+  int32_t N;
+  int32_t n_v;
+  int32_t n_h;
+  int32_t ac_conv;   /* HIPREC_CASER_AC_* */
+  int32_t ac_fc;
+} hiprec_caser_shape;
+size_t hiprec_caser_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_caser_param_floats(const hiprec_caser_shape* shape);
+/* bytes of device workspace a hiprec_caser_grad call on `batch` rows needs (0: unsupported); it depends on neither
+ * n_items nor n_users */
+size_t hiprec_caser_workspace_bytes(const hiprec_caser_shape* shape, int64_t batch);
+
+/* ---- zero_grad + forward + loss + backward of one training step on seq [batch, L], users [batch], pos [batch, T] and
+ * neg [batch, N].  Accumulates into the dense gradient g_flat (zero on entry, laid out like w_flat; the three tables
+ * by row atomics, everything else in a fixed order: the same bits on every run), adds l2 * w, leaves the loss partials
+ * in scratch and advances the step counter.
+ * keep: NULL (no dropout) or keep bytes [batch, n_v dim + n_h L] on [out_v | out_h], kept entries scaled by keep_scale.
+ * g_flat == NULL: the eval-mode forward (keep, l2 ignored; pos / neg / scratch may be NULL): x_out [batch, 2 dim].
+ * An id outside its table sets HIPREC_STATUS_ITEM_OOB / HIPREC_STATUS_USER_OOB and the entry is skipped. */
+int hiprec_caser_grad(const hiprec_caser_shape* shape, const float* w_flat, float* g_flat, const int64_t* seq,
+                      const int64_t* users, const int64_t* pos, const int64_t* neg, int64_t batch, const uint8_t* keep,
+                      float keep_scale, float l2, float* x_out, hiprec_stats* stats, void* scratch, size_t scratch_bytes,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* scores[b, k] = <x[b], W2[items[b, k]]> + b2[items[b, k]] for items [batch, n_candidates] in 1 .. n_items (anything
+ * else sets HIPREC_STATUS_ITEM_OOB and yields 0) */
+int hiprec_caser_score(const hiprec_caser_shape* shape, const float* w_flat, const float* x, const int64_t* items,
+                       int64_t batch, int32_t n_candidates, float* scores, hiprec_stats* stats, void* stream);
+
 /* ================= VBCAR (beta_rec/models/vbcar.py) ================================================
  * The parameters live in ONE flat buffer in state_dict() order: user_emb [n_users, emb_dim], item_emb [n_items, emb_dim],
  * fc_u_1_mu.weight [late_dim, fea_u], .bias [late_dim], fc_u_2_mu.weight [2 emb_dim, late_dim], .bias [2 emb_dim], then
