@@ -246,6 +246,13 @@ class NarmShape(Structure):
     _fields_ = [("n_items", c_int64), ("emb_dim", c_int32), ("hidden", c_int32), ("n_layers", c_int32), ("_pad", c_int32)]
 
 
+class Gru4recShape(Structure):
+    """hiprec_gru4rec_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_items", c_int64), ("n_layers", c_int32), ("hidden", c_int32 * 3), ("emb_dim", c_int32),
+                ("loss", c_int32)]
+
+
 class CaserShape(Structure):
     """hiprec_caser_shape (include/hiprec.h)."""
 
@@ -612,6 +619,14 @@ SIGNATURES = {
          _P],
     ),
     "hiprec_caser_score": (c_int, [POINTER(CaserShape), _P, _P, _P, c_int64, c_int32, _P, _P, _P]),
+    "hiprec_gru4rec_shape_bytes": (c_size_t, []),
+    "hiprec_gru4rec_param_floats": (c_int64, [POINTER(Gru4recShape)]),
+    "hiprec_gru4rec_workspace_bytes": (c_size_t, [POINTER(Gru4recShape), c_int64, c_int32]),
+    "hiprec_gru4rec_grad": (
+        c_int,
+        [POINTER(Gru4recShape), _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, _P, c_float, c_float, c_float, c_float, _P,
+         c_float, c_float, _P, _P, _P, c_size_t, _P, c_size_t, _P],
+    ),
     "hiprec_vbcar_shape_bytes": (c_size_t, []),
     "hiprec_vbcar_param_floats": (c_int64, [POINTER(VbcarShape)]),
     "hiprec_vbcar_workspace_bytes": (c_size_t, [POINTER(VbcarShape), c_int64, c_int32]),
@@ -867,6 +882,8 @@ def load():
         raise RuntimeError("hiprec_narm_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_caser_shape_bytes() != ctypes.sizeof(CaserShape):
         raise RuntimeError("hiprec_caser_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_gru4rec_shape_bytes() != ctypes.sizeof(Gru4recShape):
+        raise RuntimeError("hiprec_gru4rec_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vbcar_shape_bytes() != ctypes.sizeof(VbcarShape):
         raise RuntimeError("hiprec_vbcar_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_tvbr_shape_bytes() != ctypes.sizeof(TvbrShape):

@@ -440,6 +440,95 @@ class SessionLoader:
                    lens.tolist())
 
 
+# ---- session-parallel mini-batches for GRU4Rec (Hidasi et al., ICLR 2016, section 3.1) -------------------------------------
+class SessionParallelLoader:
+    """``batch_size`` slots each walk one session, one event per step; a step is ``(in_items [B], targets [B],
+    reset [B] uint8, samples [n_sample])``.
+
+    ``sessions``: a ragged list of id lists (ids in ``0 .. n_items - 1``, time order); sessions shorter than 2 are dropped
+    with a warning.  Slots take the sessions in order.  A slot whose session has no next event takes the next unused
+    session and sets ``reset`` for that step (every slot's first step has it set); the epoch ends when a slot cannot be
+    refilled, so every step is full.  The walk is built on the host once: ``in_items``, ``targets``, ``reset`` are
+    ``[n_steps, B]`` arrays.  The extra samples of an epoch, ``[n_steps, n_sample]``, are drawn with probability
+    proportional to ``support ** sample_alpha`` from ``np.random.default_rng(seed + epoch)`` (``epoch`` counts the
+    iterations of this loader).  The arrays are uploaded to ``device`` once per epoch and iterated as slices of them
+    (``device=None``: host tensors; ``GRU4RecEngine.train_an_epoch`` sets the model's device on such a loader).
+
+    ``support [n_items]``: events per item over the kept sessions; ``item_probs``: its share, which the engine's logQ
+    shift reads."""
+
+    def __init__(self, sessions, n_items, batch_size, n_sample, sample_alpha, seed=0, device=None):
+        import warnings
+
+        self.n_items, self.batch_size, self.n_sample = int(n_items), int(batch_size), int(n_sample)
+        self.sample_alpha, self.seed, self.device = float(sample_alpha), int(seed), device
+        if self.n_items < 1 or self.batch_size < 1 or self.n_sample < 0:
+            raise ValueError("n_items and batch_size must be >= 1 and n_sample >= 0")
+        kept = [np.asarray(s, dtype=np.int64).reshape(-1) for s in sessions]
+        short = sum(1 for s in kept if s.size < 2)
+        if short:
+            warnings.warn(f"{short} sessions with fewer than 2 events were dropped")
+        kept = [s for s in kept if s.size >= 2]
+        if len(kept) < self.batch_size:
+            raise ValueError(f"{len(kept)} sessions of 2 or more events cannot fill {self.batch_size} slots")
+        events = np.concatenate(kept)
+        if int(events.min()) < 0 or int(events.max()) >= self.n_items:
+            raise IndexError(f"a session holds an item outside [0, {self.n_items})")
+        self.support = np.bincount(events, minlength=self.n_items).astype(np.int64)
+        self.item_probs = self.support / float(self.support.sum())
+        weights = self.support.astype(np.float64) ** self.sample_alpha
+        weights[self.support == 0] = 0.0      # 0 ** 0 = 1: an item without an event is never drawn
+        self._cdf = np.cumsum(weights / weights.sum())
+        self._last = int(np.flatnonzero(weights)[-1])      # where a draw beyond the rounded cdf's end lands
+        B = self.batch_size
+        sess = list(range(B))                 # the session of every slot
+        at = [0] * B                          # the slot's input event inside it
+        nxt = B
+        fresh = [1] * B
+        ins, tgts, rsts = [], [], []
+        while True:
+            for b in range(B):
+                if at[b] + 1 >= kept[sess[b]].size:
+                    if nxt >= len(kept):
+                        nxt = -1
+                        break
+                    sess[b], at[b], fresh[b] = nxt, 0, 1
+                    nxt += 1
+            if nxt < 0:
+                break
+            ins.append([kept[sess[b]][at[b]] for b in range(B)])
+            tgts.append([kept[sess[b]][at[b] + 1] for b in range(B)])
+            rsts.append(list(fresh))
+            at = [a + 1 for a in at]
+            fresh = [0] * B
+        self.in_items = np.asarray(ins, dtype=np.int64).reshape(-1, B)
+        self.targets = np.asarray(tgts, dtype=np.int64).reshape(-1, B)
+        self.reset = np.asarray(rsts, dtype=np.uint8).reshape(-1, B)
+        self.samples = None                   # [n_steps, n_sample] of the epoch drawn last
+        self.epoch = 0
+
+    def __len__(self):
+        return self.in_items.shape[0]
+
+    def draw_samples(self, epoch):
+        """The ``[n_steps, n_sample]`` extra samples of ``epoch``."""
+        rng = np.random.default_rng(self.seed + int(epoch))
+        u = rng.random((len(self), self.n_sample))
+        return np.minimum(np.searchsorted(self._cdf, u, side="right"), self._last).astype(np.int64)
+
+    def __iter__(self):
+        self.samples = self.draw_samples(self.epoch)
+        self.epoch += 1
+        arrays = [torch.from_numpy(a) for a in (self.in_items, self.targets, self.reset, self.samples)]
+        if self.device is not None:
+            arrays = [a.to(self.device) for a in arrays]
+        for t in range(len(self)):
+            yield tuple(a[t] for a in arrays)
+
+    def close(self):
+        """Owns nothing."""
+
+
 def hypergraph_laplacians(users, items, n_users, n_items):
     """The user and item hypergraph Laplacians of deprecated_data_base.py:420-452 as scipy CSR matrices:
     ``L_u = I - D_u^-1/2 H D_v^-1 H^T D_u^-1/2`` and the same with the roles swapped.  ``H`` is the binary incidence

@@ -1710,6 +1710,60 @@ int hiprec_caser_grad(const hiprec_caser_shape* shape, const float* w_flat, floa
 int hiprec_caser_score(const hiprec_caser_shape* shape, const float* w_flat, const float* x, const int64_t* items,
                        int64_t batch, int32_t n_candidates, float* scores, hiprec_stats* stats, void* stream);
 
+/* ================= GRU4Rec (Hidasi et al., ICLR 2016; Hidasi and Karatzoglou, CIKM 2018; no counterpart in the
+ * reference: tests/gru4rec_torch.py is the restatement) =========================================================
+ * Items are 0 .. n_items - 1, no id is special.  The parameters live in ONE flat buffer in state_dict() order:
+ * Wy.weight [n_items, H_last]; By.weight [n_items, 1]; E.weight [n_items, emb_dim] only when emb_dim > 0 (emb_dim == 0
+ * is the constrained form: the input of layer 0 is Wy[in_items], so in_0 = H_last); per layer i
+ * G.i.weight_ih [3 H_i, in_i], G.i.weight_hh [3 H_i, H_i], G.i.bias_ih [3 H_i], G.i.bias_hh [3 H_i] with nn.GRUCell's
+ * gate order r | z | n and in_i = H_{i-1} above layer 0.
+ * Limits: 1 .. 3 layers, every H_i and emb_dim in 1 .. 128 (any value), batch <= 2048, n_sample <= 4096.
+ * One step on in_items [batch], targets [batch], reset [batch] bytes, samples [n_sample] and the state h_l [batch, H_l]:
+ *   x = drop_e(Wy[in_items] or E[in_items]); per layer h_prev = reset ? 0 : state_l,
+ *   r = sigmoid(W_ir x + b_ir + W_hr h_prev + b_hr), z likewise, n = tanh(W_in x + b_in + r (W_hn h_prev + b_hn)),
+ *   h = (1 - z) n + z h_prev, x = state_l = drop_h(h); h_prev is a constant of the step (no gradient reaches it).
+ *   cand = [targets | samples], N = batch + n_sample >= 2, R[i, j] = <h_last[i], Wy[cand[j]]> + By[cand[j]]; row i's
+ *   positive is column i, every other column is a negative even where it names the same item.
+ *   HIPREC_GRU4REC_XE:     R' = R - shift, L = - sum_i log(softmax_j(R'[i, :])[i] + 1e-24), with
+ *                          shift[j] = logq * log_p[cand[j]] * (j < batch ? 1 : sample_alpha) (none when log_p is NULL);
+ *   HIPREC_GRU4REC_BPRMAX: R' = elu(R, elu_param) if elu_param > 0, s[i, :] = softmax of R'[i, :] over j != i,
+ *                          L = sum_i (-log(sum_{j != i} sigmoid(R'[i,i] - R'[i,j]) s[i,j] + 1e-24)
+ *                                     + bpreg sum_{j != i} R'[i,j]^2 s[i,j]), differentiated through s as well.
+ * Both losses are SUMS over the batch. */
+#define HIPREC_GRU4REC_BPRMAX 0
+#define HIPREC_GRU4REC_XE 1
+typedef struct hiprec_gru4rec_shape {
+  int64_t n_items;
+  int32_t n_layers;
+  int32_t hidden[3];   /* H_i; entries beyond n_layers are ignored */
+  int32_t emb_dim;     /* 0: constrained embedding (the input rows are Wy's) */
+  int32_t loss;        /* HIPREC_GRU4REC_* */
+} hiprec_gru4rec_shape;
+size_t hiprec_gru4rec_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_gru4rec_param_floats(const hiprec_gru4rec_shape* shape);
+/* bytes of device workspace a hiprec_gru4rec_grad call needs (0: unsupported); it does not depend on n_items */
+size_t hiprec_gru4rec_workspace_bytes(const hiprec_gru4rec_shape* shape, int64_t batch, int32_t n_sample);
+
+/* ---- zero_grad + forward + loss + backward of one session-parallel step as a fixed sequence of launches (their number
+ * depends on n_layers alone), no host sync.  Accumulates into the dense gradient g_flat (zero on entry, laid out like
+ * w_flat; Wy, By and E by row atomics, everything else in a fixed order: the same bits on every run), leaves the loss
+ * partials in scratch and advances the step counter.
+ * state: HOST array of n_layers device pointers h_l [batch, H_l]; read through `reset` (NULL: no slot restarts) and
+ * overwritten with the new state.
+ * keep: NULL, or a HOST array of 1 + n_layers device pointers (each may be NULL): keep bytes [batch, in_0] on the input
+ * rows and [batch, H_l] on every layer's output; kept entries are scaled by ks_embed / ks_hidden.
+ * g_flat == NULL: the eval step (keep, targets, samples, log_p, scratch are ignored and may be NULL): the state
+ * advances and h_out [batch, H_last] receives the last layer's output.  h_out may be NULL when training.
+ * An id outside [0, n_items) in in_items, targets or samples sets HIPREC_STATUS_ITEM_OOB; its row counts as zero and
+ * receives no gradient, and nothing outside the buffers is read or written. */
+int hiprec_gru4rec_grad(const hiprec_gru4rec_shape* shape, const float* w_flat, float* g_flat, float* const* state,
+                        const int64_t* in_items, const int64_t* targets, const uint8_t* reset, const int64_t* samples,
+                        int64_t batch, int32_t n_sample, const float* log_p, float logq, float sample_alpha, float bpreg,
+                        float elu_param, const uint8_t* const* keep, float ks_embed, float ks_hidden, float* h_out,
+                        hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ================= VBCAR (beta_rec/models/vbcar.py) ================================================
  * The parameters live in ONE flat buffer in state_dict() order: user_emb [n_users, emb_dim], item_emb [n_items, emb_dim],
  * fc_u_1_mu.weight [late_dim, fea_u], .bias [late_dim], fc_u_2_mu.weight [2 emb_dim, late_dim], .bias [2 emb_dim], then
