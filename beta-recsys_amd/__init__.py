@@ -25,6 +25,7 @@ from .narm import NARM, NARMEngine  # noqa: F401
 from .bert4rec import BERT4Rec, BERT4RecEngine  # noqa: F401
 from .caser import Caser, CaserEngine  # noqa: F401
 from .gru4rec import GRU4Rec, GRU4RecEngine  # noqa: F401
+from .srgnn import SRGNN, SRGNNEngine  # noqa: F401
 from .triple2vec import Triple2vec, Triple2vecEngine  # noqa: F401
 from .vbcar import VBCAR, VBCAREngine  # noqa: F401
 from .vaecf import VAE, VAECFEngine  # noqa: F401

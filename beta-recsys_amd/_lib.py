@@ -260,6 +260,12 @@ class CaserShape(Structure):
                 ("N", c_int32), ("n_v", c_int32), ("n_h", c_int32), ("ac_conv", c_int32), ("ac_fc", c_int32)]
 
 
+class SrgnnShape(Structure):
+    """hiprec_srgnn_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_node", c_int64), ("hidden", c_int32), ("step", c_int32), ("nonhybrid", c_int32), ("_pad", c_int32)]
+
+
 class VbcarShape(Structure):
     """hiprec_vbcar_shape (include/hiprec.h)."""
 
@@ -627,6 +633,16 @@ SIGNATURES = {
         [POINTER(Gru4recShape), _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, _P, c_float, c_float, c_float, c_float, _P,
          c_float, c_float, _P, _P, _P, c_size_t, _P, c_size_t, _P],
     ),
+    "hiprec_srgnn_shape_bytes": (c_size_t, []),
+    "hiprec_srgnn_param_floats": (c_int64, [POINTER(SrgnnShape)]),
+    "hiprec_srgnn_workspace_bytes": (c_size_t, [POINTER(SrgnnShape), c_int64, c_int32, c_int64]),
+    "hiprec_srgnn_graph_ints": (c_int64, [c_int64, c_int32, c_int64]),
+    "hiprec_srgnn_graph": (c_int, [POINTER(SrgnnShape), _P, _P, c_int64, c_int32, c_int64, _P, c_size_t, _P, _P]),
+    "hiprec_srgnn_grad": (
+        c_int,
+        [POINTER(SrgnnShape), _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, c_float, _P, _P, _P, c_size_t, _P, c_size_t,
+         _P],
+    ),
     "hiprec_vbcar_shape_bytes": (c_size_t, []),
     "hiprec_vbcar_param_floats": (c_int64, [POINTER(VbcarShape)]),
     "hiprec_vbcar_workspace_bytes": (c_size_t, [POINTER(VbcarShape), c_int64, c_int32]),
@@ -884,6 +900,8 @@ def load():
         raise RuntimeError("hiprec_caser_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_gru4rec_shape_bytes() != ctypes.sizeof(Gru4recShape):
         raise RuntimeError("hiprec_gru4rec_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_srgnn_shape_bytes() != ctypes.sizeof(SrgnnShape):
+        raise RuntimeError("hiprec_srgnn_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vbcar_shape_bytes() != ctypes.sizeof(VbcarShape):
         raise RuntimeError("hiprec_vbcar_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_tvbr_shape_bytes() != ctypes.sizeof(TvbrShape):

@@ -407,9 +407,13 @@ class SessionLoader:
     (seq_data_utils.py:131-179): the batches in order; within a batch the sessions sorted by length, descending and
     stable; the ids zero-padded to the batch's longest and time-major ``[T, B]`` int64, the labels ``[B]`` in the sorted
     order, the lengths as a list.  Re-iterable: one loader serves every epoch.  The ragged arrays are built once; a batch
-    is cut from them with array operations only."""
+    is cut from them with array operations only.
 
-    def __init__(self, out_seqs, labels, batch_size):
+    ``shuffle=True`` (SR-GNN's published training; NARM's does not shuffle): the sessions are permuted by
+    ``np.random.default_rng(seed)`` before they are cut into batches, anew at every iteration of the loader (the
+    generator lives as long as the loader, so the epochs differ and one seed gives one run)."""
+
+    def __init__(self, out_seqs, labels, batch_size, shuffle=False, seed=None):
         if len(out_seqs) != len(labels):
             raise ValueError("one label per session is needed")
         if int(batch_size) < 1:
@@ -422,14 +426,21 @@ class SessionLoader:
                       else np.zeros(0, dtype=np.int64))
         self._start = np.concatenate([[0], np.cumsum(self._lens)[:-1]]).astype(np.int64) if len(out_seqs) else self._lens
         self._labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+        self.shuffle = bool(shuffle)
+        self._rng = np.random.default_rng(seed) if self.shuffle else None
 
     def __len__(self):
         return (self._lens.size + self.batch_size - 1) // self.batch_size
 
     def __iter__(self):
+        perm = self._rng.permutation(self._lens.size) if self.shuffle else None
         for lo in range(0, self._lens.size, self.batch_size):
             hi = min(lo + self.batch_size, self._lens.size)
-            order = lo + np.argsort(-self._lens[lo:hi], kind="stable")
+            if perm is None:
+                order = lo + np.argsort(-self._lens[lo:hi], kind="stable")
+            else:
+                chunk = perm[lo:hi]
+                order = chunk[np.argsort(-self._lens[chunk], kind="stable")]
             lens = self._lens[order]
             T = int(lens[0])
             pos = np.arange(T, dtype=np.int64)[None, :]

@@ -1764,6 +1764,74 @@ int hiprec_gru4rec_grad(const hiprec_gru4rec_shape* shape, const float* w_flat, 
                         hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ================= SR-GNN (Wu et al., AAAI 2019; no counterpart in the reference: tests/srgnn_torch.py is the
+ * restatement) ===================================================================================================
+ * Ids: 0 = padding, 1 .. n_node - 1 = items.  The parameters live in ONE flat buffer in state_dict() order, H = hidden:
+ * embedding.weight [n_node, H]; gnn.w_ih [3H, 2H]; gnn.w_hh [3H, H]; gnn.b_ih, gnn.b_hh [3H]; gnn.b_iah, gnn.b_oah [H];
+ * gnn.linear_edge_in.{weight [H, H], bias [H]}; gnn.linear_edge_out.{weight, bias}; linear_one.{weight [H, H], bias};
+ * linear_two.{weight, bias}; linear_three.weight [1, H]; linear_transform.{weight [H, 2H], bias [H]}.
+ * Limits: H in 1 .. 128 (any value), step in 1 .. 4, seq_len in 1 .. 256, batch in 1 .. 1024, n_node >= 2.
+ * The session graph of session b with items s_0 .. s_{len-1}: nodes = the distinct ids ascending, alias[t] = node of
+ * s_t, edges = the SET of pairs (alias[t], alias[t+1]) (a self-loop counts, a repeated transition is one edge).
+ * Cell, `step` times from h = embedding[nodes] (gate order r | z | n):
+ *   a_in[v]  = b_iah + (indeg(v)  ? mean over edges (u, v) of (W_in h[u] + b_in)   : 0)
+ *   a_out[u] = b_oah + (outdeg(u) ? mean over edges (u, v) of (W_out h[v] + b_out) : 0)
+ *   gi = w_ih [a_in | a_out] + b_ih, gh = w_hh h + b_hh, r = sigmoid(gi_r + gh_r), z = sigmoid(gi_z + gh_z),
+ *   n = tanh(gi_n + r gh_n), h' = n + z (h - n)
+ * Readout: x_t = h[alias[t]], h_T = x_{len-1}, alpha_t = linear_three . sigmoid(linear_one(h_T) + linear_two(x_t)),
+ * s_g = sum_{t < len} alpha_t x_t (no softmax), a = linear_transform([s_g | h_T]) (a = s_g when nonhybrid),
+ * scores_j = a . embedding[j] for j = 1 .. n_node - 1, loss = mean CrossEntropy(scores, target - 1). */
+typedef struct hiprec_srgnn_shape {
+  int64_t n_node;
+  int32_t hidden;
+  int32_t step;
+  int32_t nonhybrid;
+  int32_t _pad;
+} hiprec_srgnn_shape;
+size_t hiprec_srgnn_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_srgnn_param_floats(const hiprec_srgnn_shape* shape);
+/* bytes of device workspace a hiprec_srgnn_grad call on `batch` sessions padded to `seq_len` whose lengths sum to at
+ * most n_rows needs (n_rows == 0: batch * seq_len, the most any such batch needs; 0: unsupported batch or length) */
+size_t hiprec_srgnn_workspace_bytes(const hiprec_srgnn_shape* shape, int64_t batch, int32_t seq_len, int64_t n_rows);
+/* int32 entries of the graph builder's output for n_rows = sum of lens (0 for an unsupported call) */
+int64_t hiprec_srgnn_graph_ints(int64_t batch, int32_t seq_len, int64_t n_rows);
+
+/* ---- the graph builder alone, two launches.  seq [seq_len, batch] TIME-MAJOR, lens [batch] each in [1, seq_len];
+ * n_rows >= sum of lens bounds the node total N and the edge slots (the host knows the lengths; N itself stays on the
+ * device).  out holds, in this order (R = n_rows, every list int32):
+ *   n_nodes [batch]        distinct ids of session b
+ *   node_off [batch + 1]   exclusive scan of n_nodes: the nodes of session b are rows node_off[b] .. node_off[b+1];
+ *                          node_off[batch] = N
+ *   slot_off [batch + 1]   exclusive scan of lens: the edge slots of session b start there
+ *   alias [seq_len, batch] node ROW of s_t (node_off[b] + its rank among the session's ids), -1 at t >= lens[b]
+ *   nodes [R]              the id of every node row, 0 in rows >= N
+ *   node_sess [R]          its session, -1 in rows >= N
+ *   node_cnt [R]           how many positions of its session name it, 0 in rows >= N
+ *   in_start, indeg [R]    row v's in-neighbours are in_idx[in_start[v] .. + indeg[v]], node rows ascending
+ *   out_start, outdeg [R]  likewise out_idx for its out-neighbours
+ *   in_idx, out_idx [R]    the lists; session b uses slots slot_off[b] .. + its edge count, -1 elsewhere
+ * An id outside [1, n_node) inside a length sets HIPREC_STATUS_ITEM_OOB and counts as id 1. */
+int hiprec_srgnn_graph(const hiprec_srgnn_shape* shape, const int64_t* seq, const int64_t* lens, int64_t batch,
+                       int32_t seq_len, int64_t n_rows, int32_t* out, size_t out_bytes, hiprec_stats* stats,
+                       void* stream);
+
+/* ---- zero_grad + forward + loss + backward of one training step as a fixed sequence of launches (their number depends
+ * on `step` alone: launches over node rows are sized by n_rows and rows >= N fall out), no host sync.  Accumulates into
+ * the dense gradient g_flat (zero on entry, laid out like w_flat): embedding.weight[1:] is written by the scoring path
+ * and the node rows are added with row atomics, row 0 stays 0; every other gradient, the loss and the query are
+ * computed in a fixed order (the same bits on every run).  With nonhybrid, linear_transform receives nothing.  Leaves
+ * the loss partials in scratch and advances the step counter.
+ * n_rows: sum of lens (anything from there to batch * seq_len; 0 means batch * seq_len).
+ * l2: Adam's weight decay, g += l2 * w over the whole flat buffer as the last launch (none when 0); the loss excludes it.
+ * g_flat == NULL: the forward alone (target / scratch may be NULL, l2 ignored): query_out [batch, H] = a.
+ * An id outside [1, n_node) inside a length or as a target sets HIPREC_STATUS_ITEM_OOB; nothing outside the buffers is
+ * read or written. */
+int hiprec_srgnn_grad(const hiprec_srgnn_shape* shape, const float* w_flat, float* g_flat, const int64_t* seq,
+                      const int64_t* lens, const int64_t* target, int64_t batch, int32_t seq_len, int64_t n_rows,
+                      float l2, float* query_out, hiprec_stats* stats, void* scratch, size_t scratch_bytes,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ================= VBCAR (beta_rec/models/vbcar.py) ================================================
  * The parameters live in ONE flat buffer in state_dict() order: user_emb [n_users, emb_dim], item_emb [n_items, emb_dim],
  * fc_u_1_mu.weight [late_dim, fea_u], .bias [late_dim], fc_u_2_mu.weight [2 emb_dim, late_dim], .bias [2 emb_dim], then
