@@ -266,6 +266,13 @@ class SrgnnShape(Structure):
     _fields_ = [("n_node", c_int64), ("hidden", c_int32), ("step", c_int32), ("nonhybrid", c_int32), ("_pad", c_int32)]
 
 
+class NextItNetShape(Structure):
+    """hiprec_nextitnet_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_items", c_int64), ("dim", c_int32), ("kernel_size", c_int32), ("n_blocks", c_int32),
+                ("maxlen", c_int32), ("loss_last", c_int32), ("_pad", c_int32), ("dilation", c_int32 * 16)]
+
+
 class VbcarShape(Structure):
     """hiprec_vbcar_shape (include/hiprec.h)."""
 
@@ -643,6 +650,13 @@ SIGNATURES = {
         [POINTER(SrgnnShape), _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, c_float, _P, _P, _P, c_size_t, _P, c_size_t,
          _P],
     ),
+    "hiprec_nextitnet_shape_bytes": (c_size_t, []),
+    "hiprec_nextitnet_param_floats": (c_int64, [POINTER(NextItNetShape)]),
+    "hiprec_nextitnet_workspace_bytes": (c_size_t, [POINTER(NextItNetShape), c_int64, c_int32]),
+    "hiprec_nextitnet_grad": (
+        c_int, [POINTER(NextItNetShape), _P, _P, _P, _P, c_int64, c_int32, c_float, _P, _P, c_size_t, _P, c_size_t, _P]),
+    "hiprec_nextitnet_feats": (c_int, [POINTER(NextItNetShape), _P, _P, c_int64, c_int32, _P, _P, _P, c_size_t, _P]),
+    "hiprec_nextitnet_conv": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "hiprec_vbcar_shape_bytes": (c_size_t, []),
     "hiprec_vbcar_param_floats": (c_int64, [POINTER(VbcarShape)]),
     "hiprec_vbcar_workspace_bytes": (c_size_t, [POINTER(VbcarShape), c_int64, c_int32]),
@@ -902,6 +916,8 @@ def load():
         raise RuntimeError("hiprec_gru4rec_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_srgnn_shape_bytes() != ctypes.sizeof(SrgnnShape):
         raise RuntimeError("hiprec_srgnn_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_nextitnet_shape_bytes() != ctypes.sizeof(NextItNetShape):
+        raise RuntimeError("hiprec_nextitnet_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vbcar_shape_bytes() != ctypes.sizeof(VbcarShape):
         raise RuntimeError("hiprec_vbcar_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_tvbr_shape_bytes() != ctypes.sizeof(TvbrShape):

@@ -1832,6 +1832,63 @@ int hiprec_srgnn_grad(const hiprec_srgnn_shape* shape, const float* w_flat, floa
                       float l2, float* query_out, hiprec_stats* stats, void* scratch, size_t scratch_bytes,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ================= NextItNet (Yuan et al., WSDM 2019; no counterpart in the reference: tests/nextitnet_torch.py is the
+ * restatement) ===================================================================================================
+ * Ids: 0 = padding, 1 .. n_items = items; sequences are [batch, seq_len] int64, left-padded with 0.  The parameters live
+ * in ONE flat buffer in state_dict() order, D = dim, k = kernel_size: item_emb.weight [n_items + 1, D] (row 0 is zero and
+ * receives no gradient); per residual block r = 0 .. n_blocks - 1: blocks.r.conv1.weight [D, D, 1, k], conv1.bias [D],
+ * ln1.weight, ln1.bias, conv2.weight [D, D, 1, k], conv2.bias, ln2.weight, ln2.bias; final_layer.weight [D, D],
+ * final_layer.bias [D].
+ * Forward: x_0 = item_emb[seq] (no scaling, no positional row, padding positions are not masked afterwards); per block
+ * with d = dilation[r]:
+ *   c1[b, t] = conv1.bias + sum_j conv1.weight[:, :, 0, j] x[b, t - (k-1-j) d]     (x at t < 0 is 0)
+ *   h = relu(LayerNorm(c1; ln1, eps 1e-8)); c2 = the same with conv2 on h at dilation 2 d;
+ *   x_next = relu(LayerNorm(c2; ln2, eps 1e-8)) + x
+ * f = final_layer(x_R); score[m, j] = <f_m, item_emb[j]> for j = 1 .. n_items; the loss is the mean cross-entropy over the
+ * labelled rows: every row with pos != 0, or (loss_last) row seq_len - 1 of every sequence with pos != 0, each against
+ * its pos; their number is counted on the device and a batch without one gives loss 0 and a zero gradient.
+ * Limits: D a multiple of 16 up to 128, maxlen <= 256, k in 1 .. 4, n_blocks in 1 .. 16, batch * seq_len < 2^24, every
+ * dilation >= 1 (a reach beyond seq_len is legal: only the taps inside the sequence contribute). */
+typedef struct hiprec_nextitnet_shape {
+  int64_t n_items;
+  int32_t dim;
+  int32_t kernel_size;
+  int32_t n_blocks;       /* R = len(dilations) * block_num */
+  int32_t maxlen;
+  int32_t loss_last;      /* 0: every position with pos != 0 is labelled, 1: the last position of every sequence */
+  int32_t _pad;
+  int32_t dilation[16];   /* of conv1 of block r (conv2 runs at twice that); entries beyond n_blocks are ignored */
+} hiprec_nextitnet_shape;
+size_t hiprec_nextitnet_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_nextitnet_param_floats(const hiprec_nextitnet_shape* shape);
+/* bytes of device workspace a call on [batch, seq_len] needs (0: unsupported); it does not depend on n_items */
+size_t hiprec_nextitnet_workspace_bytes(const hiprec_nextitnet_shape* shape, int64_t batch, int32_t seq_len);
+
+/* ---- zero_grad + forward + loss + backward of one training step on seq and pos [batch, seq_len] as a fixed sequence of
+ * launches, no host sync.  Accumulates into the dense gradient g_flat (zero on entry, laid out like w_flat):
+ * item_emb.weight[1:] is written by the loss with plain stores and the looked-up rows are added with row atomics, row 0
+ * stays 0; every other gradient and the loss are computed in a fixed order (the same bits on every run).  Leaves the loss
+ * partials in scratch and advances the step counter.
+ * l2: the optimizer's weight decay, g += l2 * w over the whole flat buffer as the last launch (none when 0); the loss
+ * excludes it.
+ * An id outside [0, n_items] in seq or pos sets HIPREC_STATUS_ITEM_OOB; it counts as padding / as no label and nothing
+ * outside the buffers is read or written. */
+int hiprec_nextitnet_grad(const hiprec_nextitnet_shape* shape, const float* w_flat, float* g_flat, const int64_t* seq,
+                          const int64_t* pos, int64_t batch, int32_t seq_len, float l2, hiprec_stats* stats,
+                          void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
+/* the eval forward: feats_out [batch, D] = f at the last position of every sequence */
+int hiprec_nextitnet_feats(const hiprec_nextitnet_shape* shape, const float* w_flat, const int64_t* seq, int64_t batch,
+                           int32_t seq_len, float* feats_out, hiprec_stats* stats, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
+/* one convolution stage alone (tools/bench_nextitnet.py times it against the im2col + GEMM form):
+ * out = relu(LayerNorm(conv(x; weight [dim, dim, 1, kernel_size], bias, dilation); ln_weight, ln_bias, eps 1e-8)) + resid
+ * on x, out and resid (may be NULL) [batch, seq_len, dim]; the limits are the model's */
+int hiprec_nextitnet_conv(const float* x, const float* weight, const float* bias, const float* ln_weight,
+                          const float* ln_bias, const float* resid, int64_t batch, int32_t seq_len, int32_t dim,
+                          int32_t kernel_size, int32_t dilation, float* out, void* stream);
+
 /* ================= VBCAR (beta_rec/models/vbcar.py) ================================================
  * The parameters live in ONE flat buffer in state_dict() order: user_emb [n_users, emb_dim], item_emb [n_items, emb_dim],
  * fc_u_1_mu.weight [late_dim, fea_u], .bias [late_dim], fc_u_2_mu.weight [2 emb_dim, late_dim], .bias [2 emb_dim], then
