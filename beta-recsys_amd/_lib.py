@@ -273,6 +273,12 @@ class NextItNetShape(Structure):
                 ("maxlen", c_int32), ("loss_last", c_int32), ("_pad", c_int32), ("dilation", c_int32 * 16)]
 
 
+class FmlprecShape(Structure):
+    """hiprec_fmlprec_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_items", c_int64), ("dim", c_int32), ("maxlen", c_int32), ("n_blocks", c_int32), ("ffn_dim", c_int32)]
+
+
 class VbcarShape(Structure):
     """hiprec_vbcar_shape (include/hiprec.h)."""
 
@@ -657,6 +663,17 @@ SIGNATURES = {
         c_int, [POINTER(NextItNetShape), _P, _P, _P, _P, c_int64, c_int32, c_float, _P, _P, c_size_t, _P, c_size_t, _P]),
     "hiprec_nextitnet_feats": (c_int, [POINTER(NextItNetShape), _P, _P, c_int64, c_int32, _P, _P, _P, c_size_t, _P]),
     "hiprec_nextitnet_conv": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "hiprec_fmlprec_shape_bytes": (c_size_t, []),
+    "hiprec_fmlprec_param_floats": (c_int64, [POINTER(FmlprecShape)]),
+    "hiprec_fmlprec_workspace_bytes": (c_size_t, [POINTER(FmlprecShape), c_int64]),
+    "hiprec_fmlprec_twiddle": (c_int, [c_int32, _P]),
+    "hiprec_fmlprec_grad": (
+        c_int, [POINTER(FmlprecShape), _P, _P, _P, _P, _P, c_int64, _P, _P, c_float, _P, _P, _P, c_size_t, _P, c_size_t,
+                _P]),
+    "hiprec_fmlprec_feats": (c_int, [POINTER(FmlprecShape), _P, _P, c_int64, _P, _P, _P, _P, c_size_t, _P]),
+    "hiprec_fmlprec_filter_scratch_floats": (c_int64, [c_int64, c_int32, c_int32]),
+    "hiprec_fmlprec_filter": (
+        c_int, [_P, _P, _P, _P, c_float, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_size_t, _P]),
     "hiprec_vbcar_shape_bytes": (c_size_t, []),
     "hiprec_vbcar_param_floats": (c_int64, [POINTER(VbcarShape)]),
     "hiprec_vbcar_workspace_bytes": (c_size_t, [POINTER(VbcarShape), c_int64, c_int32]),
@@ -918,6 +935,8 @@ def load():
         raise RuntimeError("hiprec_srgnn_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_nextitnet_shape_bytes() != ctypes.sizeof(NextItNetShape):
         raise RuntimeError("hiprec_nextitnet_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_fmlprec_shape_bytes() != ctypes.sizeof(FmlprecShape):
+        raise RuntimeError("hiprec_fmlprec_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vbcar_shape_bytes() != ctypes.sizeof(VbcarShape):
         raise RuntimeError("hiprec_vbcar_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_tvbr_shape_bytes() != ctypes.sizeof(TvbrShape):

@@ -80,14 +80,14 @@ __global__ __launch_bounds__(kBlock) void seq_embed_kernel(const float* __restri
   }
 }
 
-// ---- LayerNorm (eps 1e-8, biased variance), one wave per row, D <= 128 -----------------------------------------------
+// ---- LayerNorm (eps 1e-8 unless the caller states its own, biased variance), one wave per row, D <= 128 -----------------------------------------------
 // x = (a + b) * (seq != 0); xsum (optional) receives x; y = (x - mean) * rstd * gamma + beta
 __global__ __launch_bounds__(kBlock) void seq_ln_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                             const int64_t* __restrict__ seq, float* __restrict__ xsum,
                                                             const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, float* __restrict__ y,
                                                             float* __restrict__ mean, float* __restrict__ rstd,
-                                                            int64_t M, int D) {
+                                                            int64_t M, int D, float eps) {
   const int lane = lane_id();
   const float inv_d = 1.f / static_cast<float>(D);
   for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block(); row < M;
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(kBlock) void seq_ln_fwd_kernel(const float* __restr
     const float mu = wave_sum(v[0] + v[1]) * inv_d;
     const float c0 = lane < D ? v[0] - mu : 0.f, c1 = lane + 64 < D ? v[1] - mu : 0.f;
     const float var = wave_sum(c0 * c0 + c1 * c1) * inv_d;
-    const float r = 1.0f / sqrtf(var + 1e-8f);
+    const float r = 1.0f / sqrtf(var + eps);
     if (lane < D) y[row * D + lane] = c0 * r * gamma[lane] + beta[lane];
     if (lane + 64 < D) y[row * D + lane + 64] = c1 * r * gamma[lane + 64] + beta[lane + 64];
     if (lane == 0) {
@@ -282,8 +282,8 @@ int seq_embed(const float* E, const float* P, const int64_t* seq, int64_t M, int
 }
 
 int seq_ln_fwd(const float* a, const float* b, const int64_t* seq, float* xsum, const float* gamma, const float* beta,
-               float* y, float* mean, float* rstd, int64_t M, int D, hipStream_t st) {
-  seq_ln_fwd_kernel<<<grid_for_waves(M), kBlock, 0, st>>>(a, b, seq, xsum, gamma, beta, y, mean, rstd, M, D);
+               float* y, float* mean, float* rstd, int64_t M, int D, hipStream_t st, float eps) {
+  seq_ln_fwd_kernel<<<grid_for_waves(M), kBlock, 0, st>>>(a, b, seq, xsum, gamma, beta, y, mean, rstd, M, D, eps);
   HIPREC_TRY(hipGetLastError());
   return 0;
 }

@@ -1889,6 +1889,67 @@ int hiprec_nextitnet_conv(const float* x, const float* weight, const float* bias
                           const float* ln_bias, const float* resid, int64_t batch, int32_t seq_len, int32_t dim,
                           int32_t kernel_size, int32_t dilation, float* out, void* stream);
 
+/* ================= FMLP-Rec (Zhou et al., WWW 2022; no counterpart in the reference: tests/fmlprec_torch.py is the
+ * restatement) ===================================================================================================
+ * Ids: 0 = padding, 1 .. n_items = items; sequences are [batch, maxlen] int64, left-padded with 0 (the length is ALWAYS
+ * maxlen: the filter has F = maxlen / 2 + 1 bins).  The parameters live in ONE flat buffer in state_dict() order, D = dim,
+ * H = ffn_dim: item_emb.weight [n_items + 1, D] (row 0 is zero and receives no gradient), pos_emb.weight [maxlen, D],
+ * emb_norm.weight, emb_norm.bias [D]; per block l: blocks.l.filter.complex_weight [F, D, 2] (real, imaginary),
+ * norm1.weight, norm1.bias, fc1.weight [H, D], fc1.bias [H], fc2.weight [D, H], fc2.bias [D], norm2.weight, norm2.bias.
+ * Forward: x = drop(LN(item_emb[seq] + pos_emb[t])) -- padded positions are NOT masked, they carry pos_emb[t] --; per
+ * block h = LN1(x + drop(filter(x))), x = LN2(h + drop(fc2(gelu(fc1(h))))) (exact erf GELU, every LayerNorm eps 1e-12);
+ * f = x at the last position.  filter(x) = irfft(rfft(x, ortho) * W, n = maxlen, ortho) along the positions, computed as
+ * two dense real products against the basis cos / sin(2 pi (k t mod T) / T): with s = 1 / sqrt(T), m_k = 1 for k = 0 and
+ * (T even) k = T / 2, else 2:  Xr = s sum_t cos x, Xi = -s sum_t sin x; Y = X W (complex);
+ * y[t] = s sum_k m_k (Yr cos - Yi sin).
+ * Loss: the mean over the rows with pos != 0 of softplus(-<f, E[pos]>) + softplus(<f, E[neg]>) (the published
+ * -log(sigmoid + 1e-24) in its stable form); no such row gives loss 0 and a zero gradient.  No regulariser.
+ * Limits: D a multiple of 16 in 16 .. 128, maxlen in 1 .. 256, n_blocks in 1 .. 16, ffn_dim a multiple of 16 in
+ * 16 .. 512, batch * maxlen <= 2^24. */
+typedef struct hiprec_fmlprec_shape {
+  int64_t n_items;
+  int32_t dim;
+  int32_t maxlen;
+  int32_t n_blocks;
+  int32_t ffn_dim;
+} hiprec_fmlprec_shape;
+size_t hiprec_fmlprec_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_fmlprec_param_floats(const hiprec_fmlprec_shape* shape);
+/* bytes of device workspace a call on [batch, maxlen] needs (0: unsupported); it does not depend on n_items */
+size_t hiprec_fmlprec_workspace_bytes(const hiprec_fmlprec_shape* shape, int64_t batch);
+/* HOST: out[2 j], out[2 j + 1] = cos, sin(2 pi j / seq_len) for j < seq_len, evaluated in double, exact on the axes.  The
+ * caller copies the table to the device once per length and passes it as `twiddle` below (8-byte aligned). */
+int hiprec_fmlprec_twiddle(int32_t seq_len, float* out);
+
+/* ---- zero_grad + forward + loss + backward of one training step on seq [batch, maxlen], pos and neg [batch] as a fixed
+ * sequence of launches, no host sync.  Accumulates into the dense gradient g_flat (zero on entry, laid out like w_flat):
+ * item_emb.weight receives row atomics (row 0 stays 0); every other gradient is computed in a fixed order (the same bits on
+ * every run).  Leaves the loss partials in scratch and advances the step counter.
+ * keep: NULL (no dropout) or 1 + 2 n_blocks device pointers to [batch * maxlen, D] keep bytes -- embedding, then per block
+ * the filter's and the feed-forward's output --, kept values are scaled by keep_scale.
+ * feats_out (optional) [batch, D] receives f.
+ * An id outside [0, n_items] in seq, pos or neg sets HIPREC_STATUS_ITEM_OOB; it counts as padding / as no label and nothing
+ * outside the buffers is read or written. */
+int hiprec_fmlprec_grad(const hiprec_fmlprec_shape* shape, const float* w_flat, float* g_flat, const int64_t* seq,
+                        const int64_t* pos, const int64_t* neg, int64_t batch, const float* twiddle,
+                        const uint8_t* const* keep, float keep_scale, float* feats_out, hiprec_stats* stats, void* scratch,
+                        size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
+/* the eval forward: feats_out [batch, D] = f */
+int hiprec_fmlprec_feats(const hiprec_fmlprec_shape* shape, const float* w_flat, const int64_t* seq, int64_t batch,
+                         const float* twiddle, float* feats_out, hiprec_stats* stats, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* the filter stage alone on x [batch, seq_len, dim] with weight [seq_len / 2 + 1, dim, 2] and the table of seq_len:
+ * y (if not NULL) = keep(filter(x)) (keep may be NULL); with dy (the gradient of filter(x)) also dx = its input gradient
+ * and dw = its weight gradient summed over the batch in a fixed order, through `scratch` of at least
+ * hiprec_fmlprec_filter_scratch_floats(batch, seq_len, dim) floats (-1: shape outside the model's limits).  x, weight, dw
+ * and scratch are 8-byte aligned. */
+int64_t hiprec_fmlprec_filter_scratch_floats(int64_t batch, int32_t seq_len, int32_t dim);
+int hiprec_fmlprec_filter(const float* x, const float* weight, const float* twiddle, const uint8_t* keep, float keep_scale,
+                          const float* dy, int64_t batch, int32_t seq_len, int32_t dim, float* y, float* dx, float* dw,
+                          float* scratch, size_t scratch_floats, void* stream);
+
 /* ================= VBCAR (beta_rec/models/vbcar.py) ================================================
  * The parameters live in ONE flat buffer in state_dict() order: user_emb [n_users, emb_dim], item_emb [n_items, emb_dim],
  * fc_u_1_mu.weight [late_dim, fea_u], .bias [late_dim], fc_u_2_mu.weight [2 emb_dim, late_dim], .bias [2 emb_dim], then
