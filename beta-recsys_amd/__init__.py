@@ -28,6 +28,7 @@ from .gru4rec import GRU4Rec, GRU4RecEngine  # noqa: F401
 from .srgnn import SRGNN, SRGNNEngine  # noqa: F401
 from .nextitnet import NextItNet, NextItNetEngine  # noqa: F401
 from .fmlprec import FMLPRec, FMLPRecEngine  # noqa: F401
+from .hstu import HSTU, HSTUEngine  # noqa: F401
 from .triple2vec import Triple2vec, Triple2vecEngine  # noqa: F401
 from .vbcar import VBCAR, VBCAREngine  # noqa: F401
 from .vaecf import VAE, VAECFEngine  # noqa: F401

@@ -279,6 +279,14 @@ class FmlprecShape(Structure):
     _fields_ = [("n_items", c_int64), ("dim", c_int32), ("maxlen", c_int32), ("n_blocks", c_int32), ("ffn_dim", c_int32)]
 
 
+class HstuShape(Structure):
+    """hiprec_hstu_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_items", c_int64), ("dim", c_int32), ("heads", c_int32), ("attention_dim", c_int32),
+                ("linear_dim", c_int32), ("maxlen", c_int32), ("n_blocks", c_int32), ("num_buckets", c_int32),
+                ("rel_bias", c_int32)]
+
+
 class VbcarShape(Structure):
     """hiprec_vbcar_shape (include/hiprec.h)."""
 
@@ -599,6 +607,7 @@ SIGNATURES = {
     "hiprec_sasrec_shape_bytes": (c_size_t, []),
     "hiprec_sasrec_param_floats": (c_int64, [POINTER(SasrecShape)]),
     "hiprec_sasrec_workspace_bytes": (c_size_t, [POINTER(SasrecShape), c_int64, c_int32]),
+    "hiprec_sasrec_attention": (c_int, [_P, _P, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P]),
     "hiprec_sasrec_grad": (
         c_int,
         [POINTER(SasrecShape), _P, _P, _P, _P, _P, c_int64, c_int32, c_float, _P, c_float, _P, _P, _P, c_size_t, _P,
@@ -674,6 +683,19 @@ SIGNATURES = {
     "hiprec_fmlprec_filter_scratch_floats": (c_int64, [c_int64, c_int32, c_int32]),
     "hiprec_fmlprec_filter": (
         c_int, [_P, _P, _P, _P, c_float, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_size_t, _P]),
+    "hiprec_hstu_shape_bytes": (c_size_t, []),
+    "hiprec_hstu_param_floats": (c_int64, [POINTER(HstuShape)]),
+    "hiprec_hstu_workspace_bytes": (c_size_t, [POINTER(HstuShape), c_int64, c_int32]),
+    "hiprec_hstu_time_thresholds": (c_int, [c_int32, _P]),
+    "hiprec_hstu_grad": (
+        c_int, [POINTER(HstuShape), _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_float, _P, c_float, _P, _P, _P, c_size_t,
+                _P, c_size_t, _P]),
+    "hiprec_hstu_feats": (c_int, [POINTER(HstuShape), _P, _P, _P, c_int64, c_int32, _P, _P, _P, c_size_t, _P]),
+    "hiprec_hstu_buckets": (c_int, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P]),
+    "hiprec_hstu_attention_scratch_floats": (c_int64, [c_int64, c_int32, c_int32, c_int32]),
+    "hiprec_hstu_attention": (
+        c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
+                c_size_t, _P]),
     "hiprec_vbcar_shape_bytes": (c_size_t, []),
     "hiprec_vbcar_param_floats": (c_int64, [POINTER(VbcarShape)]),
     "hiprec_vbcar_workspace_bytes": (c_size_t, [POINTER(VbcarShape), c_int64, c_int32]),
@@ -937,6 +959,8 @@ def load():
         raise RuntimeError("hiprec_nextitnet_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_fmlprec_shape_bytes() != ctypes.sizeof(FmlprecShape):
         raise RuntimeError("hiprec_fmlprec_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_hstu_shape_bytes() != ctypes.sizeof(HstuShape):
+        raise RuntimeError("hiprec_hstu_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vbcar_shape_bytes() != ctypes.sizeof(VbcarShape):
         raise RuntimeError("hiprec_vbcar_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_tvbr_shape_bytes() != ctypes.sizeof(TvbrShape):

@@ -47,6 +47,14 @@ __global__ __launch_bounds__(kBlock) void sas_embed_bwd_kernel(const float* __re
   g_pos[e] += acc;
 }
 
+int seq_embed_bwd(const float* dx, const int64_t* seq, int64_t B, int T, int D, int64_t n_items, float sqrt_d,
+                  const uint8_t* keep, float ks, float* g_item, float* g_pos, hipStream_t st) {
+  sas_embed_bwd_kernel<<<(T * D + kBlock - 1) / kBlock, kBlock, 0, st>>>(dx, seq, B, T, D, n_items, sqrt_d, keep, ks,
+                                                                         g_item, g_pos);
+  HIPREC_TRY(hipGetLastError());
+  return 0;
+}
+
 // ---- causal attention per (sequence, head) ----------------------------------------------------------------------------
 constexpr int kSasQT = 32;                 // query (or key) rows a block owns
 constexpr int kSasSLd = kSeqMaxLen + 4;    // leading dimension of the score rows in LDS
@@ -504,10 +512,7 @@ static int sas_run(const hiprec_sasrec_shape& s, float* w_flat, float* g_flat, c
                             g.ln_a_b[k], a.cs, M, D, st))
       return rc;
   }
-  sas_embed_bwd_kernel<<<(T * D + kBlock - 1) / kBlock, kBlock, 0, st>>>(T2, seq, B, T, D, s.n_items, sqrt_d, kp(0), ks,
-                                                                         g.item_emb, g.pos_emb);
-  HIPREC_TRY(hipGetLastError());
-  return 0;
+  return seq_embed_bwd(T2, seq, B, T, D, s.n_items, sqrt_d, kp(0), ks, g.item_emb, g.pos_emb, st);
 }
 
 }  // namespace hiprec
@@ -524,6 +529,28 @@ extern "C" int64_t hiprec_sasrec_param_floats(const hiprec_sasrec_shape* shape) 
 extern "C" size_t hiprec_sasrec_workspace_bytes(const hiprec_sasrec_shape* shape, int64_t batch, int32_t seq_len) {
   if (sas_check_shape(shape) || batch <= 0 || seq_len <= 0) return 0;
   return sizeof(float) * static_cast<size_t>(sas_carve(nullptr, *shape, batch, seq_len).floats);
+}
+
+extern "C" int hiprec_sasrec_attention(const float* qkv, const float* d_out, int64_t batch, int32_t seq_len, int32_t heads,
+                                       int32_t dim, float* out, float* lse, float* delta, float* dqkv, void* stream) {
+  HIPREC_REQUIRE(qkv && out && lse && (!d_out || (delta && dqkv)), "NULL pointer");
+  HIPREC_REQUIRE(!seq_check_shape("SASRec", 1, 1, heads, seq_len, dim) && batch >= 1 && batch * seq_len < (1ll << 24),
+                 "SASRec attention: shape outside the model's limits");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid(static_cast<unsigned>(batch * heads), static_cast<unsigned>((seq_len + kSasQT - 1) / kSasQT));
+  return by_head_width(dim / heads, [&](auto hw) {
+    constexpr int HD = decltype(hw)::value;
+    if (!d_out) {
+      sas_attn_fwd_kernel<HD><<<grid, kBlock, 0, st>>>(qkv, seq_len, heads, dim, nullptr, 1.f, out, lse);
+    } else {
+      sas_attn_bwd_q_kernel<HD><<<grid, kBlock, 0, st>>>(qkv, d_out, out, lse, seq_len, heads, dim, nullptr, 1.f, delta,
+                                                         dqkv);
+      HIPREC_TRY(hipGetLastError());
+      sas_attn_bwd_kv_kernel<HD><<<grid, kBlock, 0, st>>>(qkv, d_out, lse, delta, seq_len, heads, dim, nullptr, 1.f, dqkv);
+    }
+    HIPREC_TRY(hipGetLastError());
+    return 0;
+  });
 }
 
 extern "C" int hiprec_sasrec_grad(const hiprec_sasrec_shape* shape, const float* w_flat, float* g_flat,

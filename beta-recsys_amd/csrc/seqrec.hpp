@@ -64,6 +64,9 @@ int seq_prep(const float* W, float* g, int64_t n_w, const int64_t* pos, int64_t 
 // x = (E[seq] * sqrt(D) + P[t]) * keep * (seq != 0); P == NULL: no positional row
 int seq_embed(const float* E, const float* P, const int64_t* seq, int64_t M, int T, int D, int64_t n_items,
               float sqrt_d, const uint8_t* keep, float ks, float* x, hiprec_stats* stats, hipStream_t st);
+// the embed backward (csrc/sasrec.hip): row atomics into g_item (id 0 skipped), g_pos += the batch sum in a fixed order
+int seq_embed_bwd(const float* dx, const int64_t* seq, int64_t B, int T, int D, int64_t n_items, float sqrt_d,
+                  const uint8_t* keep, float ks, float* g_item, float* g_pos, hipStream_t st);
 // eps: the LayerNorm's (1e-8, the SASRec family's, unless a model states its own)
 int seq_ln_fwd(const float* a, const float* b, const int64_t* seq, float* xsum, const float* gamma, const float* beta,
                float* y, float* mean, float* rstd, int64_t M, int D, hipStream_t st, float eps = 1e-8f);

@@ -1516,6 +1516,12 @@ int hiprec_sasrec_grad(const hiprec_sasrec_shape* shape, const float* w_flat, fl
                        const int64_t* pos, const int64_t* neg, int64_t batch, int32_t seq_len, float l2_emb,
                        const uint8_t* const* keep, float keep_scale, float* feats_out, hiprec_stats* stats,
                        void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
+/* the causal softmax attention stage alone on qkv [batch * seq_len, 3 dim] = q | k | v (no dropout), for timing it next to
+ * other attention stages (tools/bench_hstu.py).  d_out NULL: the forward, out [batch * seq_len, dim] and lse
+ * [batch * heads, seq_len].  With d_out (the gradient of out; out and lse from a forward call): the two backward kernels,
+ * delta [batch * heads, seq_len] and dqkv [batch * seq_len, 3 dim].  The limits are the model's. */
+int hiprec_sasrec_attention(const float* qkv, const float* d_out, int64_t batch, int32_t seq_len, int32_t heads, int32_t dim,
+                            float* out, float* lse, float* delta, float* dqkv, void* stream);
 
 /* ================= TiSASRec (beta_rec/models/tisasrec.py) ==========================================
  * The parameters live in ONE flat buffer in state_dict() order: item_emb [n_items + 1, dim] (row 0 = padding),
@@ -1949,6 +1955,77 @@ int64_t hiprec_fmlprec_filter_scratch_floats(int64_t batch, int32_t seq_len, int
 int hiprec_fmlprec_filter(const float* x, const float* weight, const float* twiddle, const uint8_t* keep, float keep_scale,
                           const float* dy, int64_t batch, int32_t seq_len, int32_t dim, float* y, float* dx, float* dw,
                           float* scratch, size_t scratch_floats, void* stream);
+
+/* ================= HSTU (Zhai et al., ICML 2024; no counterpart in the reference: tests/hstu_torch.py is the
+ * restatement) ===================================================================================================
+ * Ids: 0 = padding, 1 .. n_items = items; sequences are [batch, seq_len <= maxlen] int64, left-padded with 0; N = maxlen
+ * is the constant of the 1 / N and of the pos_w offset whatever seq_len is.  time_seq [batch, seq_len] int64 holds
+ * non-negative time stamps below 2^62 (only with HIPREC_HSTU_BIAS_POS_TIME; a value outside that range at a valid position
+ * sets HIPREC_STATUS_ROW_OOB).  The parameters live in ONE flat buffer in state_dict() order, D = dim, H = heads,
+ * dq = attention_dim, dv = linear_dim: item_emb.weight [n_items + 1, D] (row 0 is zero and receives no gradient),
+ * pos_emb.weight [maxlen, D]; per block l: blocks.l.norm.weight, .bias [D], blocks.l.uvqk [D, 2 H dv + 2 H dq],
+ * blocks.l.pos_w [2 maxlen - 1], blocks.l.ts_w [num_buckets + 1] (HIPREC_HSTU_BIAS_POS_TIME only), blocks.l.o.weight
+ * [D, H dv], blocks.l.o.bias [D]; last_norm.weight, .bias [D].
+ * Forward: x = (item_emb[seq] sqrt(D) + pos_emb[t]) * keep * valid; per block u | v | q | k = SiLU(LN(x) uvqk),
+ * S[i, j] = <q_i, k_j> + pos_w[N - 1 + j - i] + ts_w[bucket[i, j]], A = SiLU(S) / N where j <= i and both positions are
+ * valid, else 0; Y = LN_noaffine(A v over all H dv columns) * u through the keep bytes; x = (x + Y o.weight^T + o.bias) *
+ * valid; f = LN(x; last_norm).  Every LayerNorm has eps 1e-6.  bucket[i, j] = min(num_buckets, floor(ln(max(d, 1)) / 0.301))
+ * with d = |time_seq[min(i + 1, seq_len - 1)] - time_seq[j]|, evaluated exactly: the count of thresholds <= d.
+ * Loss: the SASRec family's BCE-with-logits over pos != 0 plus l2_emb ||item_emb||_2; no label gives loss 0.
+ * Limits: D a multiple of 16 in 16 .. 128, maxlen in 1 .. 256, n_blocks in 1 .. 16, dq and dv in (16, 32, 64), H dq and
+ * H dv <= 128, num_buckets in 1 .. 255, batch * seq_len < 2^24. */
+enum { HIPREC_HSTU_BIAS_POS_TIME = 0, HIPREC_HSTU_BIAS_POS = 1 };
+typedef struct hiprec_hstu_shape {
+  int64_t n_items;
+  int32_t dim;
+  int32_t heads;
+  int32_t attention_dim;
+  int32_t linear_dim;
+  int32_t maxlen;
+  int32_t n_blocks;
+  int32_t num_buckets;
+  int32_t rel_bias;
+} hiprec_hstu_shape;
+size_t hiprec_hstu_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_hstu_param_floats(const hiprec_hstu_shape* shape);
+/* bytes of device workspace a call on [batch, seq_len] needs (0: unsupported); it does not depend on n_items */
+size_t hiprec_hstu_workspace_bytes(const hiprec_hstu_shape* shape, int64_t batch, int32_t seq_len);
+/* HOST: out[k - 1] = the smallest integer d with floor(ln(d) / 0.301) >= k for k = 1 .. num_buckets, from the formula in
+ * double checked at each candidate's neighbours (INT64_MAX where no gap below 2^62 reaches the bucket) */
+int hiprec_hstu_time_thresholds(int32_t num_buckets, int64_t* out);
+
+/* ---- zero_grad + forward + loss + backward of one training step on seq, time_seq, pos and neg [batch, seq_len] as a fixed
+ * sequence of launches, no host sync.  Accumulates into the dense gradient g_flat (zero on entry, laid out like w_flat):
+ * item_emb.weight receives row atomics (row 0 stays 0); every other gradient is computed in a fixed order (the same bits on
+ * every run).  Leaves the loss partials in scratch and advances the step counter.
+ * keep: NULL (no dropout) or 1 + n_blocks device pointers to keep bytes -- embedding [batch * seq_len, D], then per block Y
+ * [batch * seq_len, H dv] --, kept values are scaled by keep_scale.  feats_out (optional) [batch * seq_len, D] receives f.
+ * An id outside [0, n_items] in seq, pos or neg sets HIPREC_STATUS_ITEM_OOB; it counts as padding / as no label and nothing
+ * outside the buffers is read or written. */
+int hiprec_hstu_grad(const hiprec_hstu_shape* shape, const float* w_flat, float* g_flat, const int64_t* seq,
+                     const int64_t* time_seq, const int64_t* pos, const int64_t* neg, int64_t batch, int32_t seq_len,
+                     float l2_emb, const uint8_t* const* keep, float keep_scale, float* feats_out, hiprec_stats* stats,
+                     void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
+/* the eval forward: feats_out [batch * seq_len, D] = f */
+int hiprec_hstu_feats(const hiprec_hstu_shape* shape, const float* w_flat, const int64_t* seq, const int64_t* time_seq,
+                      int64_t batch, int32_t seq_len, float* feats_out, hiprec_stats* stats, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
+/* bucket [batch, seq_len, seq_len] bytes (written for j <= i only) from time_seq, as the step computes them */
+int hiprec_hstu_buckets(const int64_t* time_seq, const int64_t* seq, int64_t batch, int32_t seq_len, int32_t num_buckets,
+                        uint8_t* bucket, hiprec_stats* stats, void* stream);
+/* the attention stage alone on act [batch * seq_len, 2 H dv + 2 H dq] = u | v | q | k (the u columns are not read), pos_w
+ * [2 maxlen - 1], ts_w [num_buckets + 1] with its bucket bytes (both NULL: no time term) and seq: av (if not NULL)
+ * [batch * seq_len, H dv] = A v; with dav (the gradient of av) also dq | dk | dv into the q, k and v columns of dact (laid
+ * out like act), and plain stores into dpos_w at the offsets j - i in -(seq_len - 1) .. 0 and into every entry of dts_w,
+ * summed in a fixed order through `scratch` of at least hiprec_hstu_attention_scratch_floats(...) floats (-1: outside the
+ * limits). */
+int64_t hiprec_hstu_attention_scratch_floats(int64_t batch, int32_t seq_len, int32_t heads, int32_t num_buckets);
+int hiprec_hstu_attention(const float* act, const float* pos_w, const float* ts_w, const int64_t* seq,
+                          const uint8_t* bucket, const float* dav, int64_t batch, int32_t seq_len, int32_t heads,
+                          int32_t attention_dim, int32_t linear_dim, int32_t maxlen, int32_t num_buckets, float* av,
+                          float* dact, float* dpos_w, float* dts_w, float* scratch, size_t scratch_floats, void* stream);
 
 /* ================= VBCAR (beta_rec/models/vbcar.py) ================================================
  * The parameters live in ONE flat buffer in state_dict() order: user_emb [n_users, emb_dim], item_emb [n_items, emb_dim],
