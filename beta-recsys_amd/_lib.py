@@ -279,6 +279,13 @@ class FmlprecShape(Structure):
     _fields_ = [("n_items", c_int64), ("dim", c_int32), ("maxlen", c_int32), ("n_blocks", c_int32), ("ffn_dim", c_int32)]
 
 
+class Mamba4RecShape(Structure):
+    """hiprec_mamba4rec_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_items", c_int64), ("dim", c_int32), ("maxlen", c_int32), ("n_blocks", c_int32), ("ffn_dim", c_int32),
+                ("d_state", c_int32), ("d_conv", c_int32), ("expand", c_int32), ("dt_rank", c_int32)]
+
+
 class HstuShape(Structure):
     """hiprec_hstu_shape (include/hiprec.h)."""
 
@@ -696,6 +703,16 @@ SIGNATURES = {
     "hiprec_hstu_attention": (
         c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
                 c_size_t, _P]),
+    "hiprec_mamba4rec_shape_bytes": (c_size_t, []),
+    "hiprec_mamba4rec_param_floats": (c_int64, [POINTER(Mamba4RecShape)]),
+    "hiprec_mamba4rec_workspace_bytes": (c_size_t, [POINTER(Mamba4RecShape), c_int64]),
+    "hiprec_mamba4rec_grad": (
+        c_int, [POINTER(Mamba4RecShape), _P, _P, _P, _P, _P, c_int64, _P, c_float, _P, _P, _P, c_size_t, _P, c_size_t, _P]),
+    "hiprec_mamba4rec_feats": (c_int, [POINTER(Mamba4RecShape), _P, _P, c_int64, _P, _P, _P, c_size_t, _P]),
+    "hiprec_mamba4rec_scan_scratch_floats": (c_int64, [c_int64, c_int32, c_int32, c_int32]),
+    "hiprec_mamba4rec_scan": (
+        c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                c_size_t, _P]),
     "hiprec_vbcar_shape_bytes": (c_size_t, []),
     "hiprec_vbcar_param_floats": (c_int64, [POINTER(VbcarShape)]),
     "hiprec_vbcar_workspace_bytes": (c_size_t, [POINTER(VbcarShape), c_int64, c_int32]),
@@ -961,6 +978,8 @@ def load():
         raise RuntimeError("hiprec_fmlprec_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_hstu_shape_bytes() != ctypes.sizeof(HstuShape):
         raise RuntimeError("hiprec_hstu_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_mamba4rec_shape_bytes() != ctypes.sizeof(Mamba4RecShape):
+        raise RuntimeError("hiprec_mamba4rec_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vbcar_shape_bytes() != ctypes.sizeof(VbcarShape):
         raise RuntimeError("hiprec_vbcar_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_tvbr_shape_bytes() != ctypes.sizeof(TvbrShape):

@@ -2027,6 +2027,71 @@ int hiprec_hstu_attention(const float* act, const float* pos_w, const float* ts_
                           int32_t attention_dim, int32_t linear_dim, int32_t maxlen, int32_t num_buckets, float* av,
                           float* dact, float* dpos_w, float* dts_w, float* scratch, size_t scratch_floats, void* stream);
 
+/* ================= Mamba4Rec (Liu et al., 2024; no counterpart in the reference: tests/mamba4rec_torch.py is the
+ * restatement) ===================================================================================================
+ * Ids: 0 = padding, 1 .. n_items = items; sequences are [batch, maxlen] int64, left-padded with 0; start[b] is the first
+ * slot with seq != 0.  D = dim, Di = expand * D, N = d_state, R = dt_rank, Kc = d_conv, H = ffn_dim.  The parameters live
+ * in ONE flat buffer in state_dict() order: item_emb.weight [n_items + 1, D] (row 0 is zero and receives no gradient),
+ * emb_norm.weight, emb_norm.bias [D]; per layer l: layers.l.mamba.in_proj.weight [2 Di, D], .conv1d.weight [Di, 1, Kc],
+ * .conv1d.bias [Di], .x_proj.weight [R + 2 N, Di], .dt_proj.weight [Di, R], .dt_proj.bias [Di], .A_log [Di, N], .D [Di],
+ * .out_proj.weight [D, Di]; layers.l.norm1.weight, .bias, fc1.weight [H, D], fc1.bias [H], fc2.weight [D, H], fc2.bias [D],
+ * norm2.weight, norm2.bias.
+ * Forward: x = LN(drop(item_emb[seq])) (no positional table); per layer, with m = (t >= start): [xi | z] = (x m) in_proj^T;
+ * u = silu(causal depthwise conv(xi) + bias); [dt | Bm | Cm] = u x_proj^T; delta = softplus(dt dt_proj^T + bias);
+ * A = -exp(A_log); h_t = exp(delta_t A) h_{t-1} + delta_t Bm_t u_t, y_t = <Cm_t, h_t> + D u_t, both held at 0 through the
+ * padded slots; mo = drop((y silu(z)) out_proj^T); h = LN1(mo + x) (n_blocks == 1: LN1(mo), as published);
+ * x = LN2(h + drop(fc2(drop(gelu(fc1(h)))))) (exact erf GELU, every LayerNorm eps 1e-12); f = x at the last slot.
+ * Loss: the mean over the rows with pos != 0 of softplus(-<f, E[pos]>) + softplus(<f, E[neg]>); no such row gives loss 0
+ * and a zero gradient.  No regulariser.
+ * Limits: D a multiple of 16 in 16 .. 128, expand 1 or 2, d_state in 1 .. 64, d_conv in 2 .. 4, dt_rank in 1 .. 32, maxlen
+ * in 1 .. 256, n_blocks in 1 .. 16, ffn_dim a multiple of 16 in 16 .. 512, batch * maxlen <= 2^24. */
+typedef struct hiprec_mamba4rec_shape {
+  int64_t n_items;
+  int32_t dim;
+  int32_t maxlen;
+  int32_t n_blocks;
+  int32_t ffn_dim;
+  int32_t d_state;
+  int32_t d_conv;
+  int32_t expand;
+  int32_t dt_rank;
+} hiprec_mamba4rec_shape;
+size_t hiprec_mamba4rec_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_mamba4rec_param_floats(const hiprec_mamba4rec_shape* shape);
+/* bytes of device workspace a call on [batch, maxlen] needs (0: unsupported); it does not depend on n_items and holds no
+ * [batch, maxlen, Di, N] term */
+size_t hiprec_mamba4rec_workspace_bytes(const hiprec_mamba4rec_shape* shape, int64_t batch);
+
+/* ---- zero_grad + forward + loss + backward of one training step on seq [batch, maxlen], pos and neg [batch] as a fixed
+ * sequence of launches, no host sync.  Accumulates into the dense gradient g_flat (zero on entry, laid out like w_flat):
+ * item_emb.weight receives row atomics (row 0 stays 0); every other gradient is computed in a fixed order (the same bits on
+ * every run).  Leaves the loss partials in scratch and advances the step counter.
+ * keep: NULL (no dropout) or 1 + 3 n_blocks device pointers to keep bytes -- embedding [batch * maxlen, D], then per layer
+ * the Mamba output [., D], the feed-forward's hidden [., H] and its output [., D] --, kept values are scaled by keep_scale.
+ * feats_out (optional) [batch, D] receives f.
+ * An id outside [0, n_items] in seq, pos or neg sets HIPREC_STATUS_ITEM_OOB; it counts as padding / as no label and nothing
+ * outside the buffers is read or written. */
+int hiprec_mamba4rec_grad(const hiprec_mamba4rec_shape* shape, const float* w_flat, float* g_flat, const int64_t* seq,
+                          const int64_t* pos, const int64_t* neg, int64_t batch, const uint8_t* const* keep,
+                          float keep_scale, float* feats_out, hiprec_stats* stats, void* scratch, size_t scratch_bytes,
+                          void* workspace, size_t workspace_bytes, void* stream);
+/* the eval forward: feats_out [batch, D] = f */
+int hiprec_mamba4rec_feats(const hiprec_mamba4rec_shape* shape, const float* w_flat, const int64_t* seq, int64_t batch,
+                           float* feats_out, hiprec_stats* stats, void* workspace, size_t workspace_bytes, void* stream);
+
+/* the selective scan alone on u, dt_pre, z [batch, seq_len, d_inner], A [d_inner, d_state] (A itself, not its log), Bm, Cm
+ * [batch, seq_len, d_state], D [d_inner] and start [batch] int32 (slots before start[b] are padding):
+ * out (if not NULL) = (scan(softplus(dt_pre), A, Bm, Cm, u) + D u) silu(z), 0 at padding; with dout also du, ddt_pre, dz, dA,
+ * dBm, dCm, dD (plain stores, summed in a fixed order) through `scratch` of at least
+ * hiprec_mamba4rec_scan_scratch_floats(...) floats (-1: d_inner a multiple of 16 up to 256, d_state up to 64, seq_len up to
+ * 256).  The [batch, seq_len, d_inner] buffers are 16-byte aligned. */
+int64_t hiprec_mamba4rec_scan_scratch_floats(int64_t batch, int32_t seq_len, int32_t d_inner, int32_t d_state);
+int hiprec_mamba4rec_scan(const float* u, const float* dt_pre, const float* z, const float* A, const float* Bm,
+                          const float* Cm, const float* D, const int32_t* start, const float* dout, int64_t batch,
+                          int32_t seq_len, int32_t d_inner, int32_t d_state, float* out, float* du, float* ddt_pre, float* dz,
+                          float* dA, float* dBm, float* dCm, float* dD, float* scratch, size_t scratch_floats, void* stream);
+
 /* ================= VBCAR (beta_rec/models/vbcar.py) ================================================
  * The parameters live in ONE flat buffer in state_dict() order: user_emb [n_users, emb_dim], item_emb [n_items, emb_dim],
  * fc_u_1_mu.weight [late_dim, fea_u], .bias [late_dim], fc_u_2_mu.weight [2 emb_dim, late_dim], .bias [2 emb_dim], then
