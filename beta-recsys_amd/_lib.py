@@ -286,6 +286,13 @@ class Mamba4RecShape(Structure):
                 ("d_state", c_int32), ("d_conv", c_int32), ("expand", c_int32), ("dt_rank", c_int32)]
 
 
+class ComirecShape(Structure):
+    """hiprec_comirec_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_items", c_int64), ("dim", c_int32), ("maxlen", c_int32), ("n_interest", c_int32),
+                ("routing_iters", c_int32)]
+
+
 class HstuShape(Structure):
     """hiprec_hstu_shape (include/hiprec.h)."""
 
@@ -713,6 +720,15 @@ SIGNATURES = {
     "hiprec_mamba4rec_scan": (
         c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                 c_size_t, _P]),
+    "hiprec_comirec_shape_bytes": (c_size_t, []),
+    "hiprec_comirec_param_floats": (c_int64, [POINTER(ComirecShape)]),
+    "hiprec_comirec_workspace_bytes": (c_size_t, [POINTER(ComirecShape), c_int64, c_int32]),
+    "hiprec_comirec_grad": (
+        c_int, [POINTER(ComirecShape), _P, _P, _P, _P, _P, c_int64, c_int32, _P, _P, _P, _P, _P, c_size_t, _P, c_size_t, _P]),
+    "hiprec_comirec_project": (c_int, [_P, _P, c_int64, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
+    "hiprec_comirec_route": (c_int, [_P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
+    "hiprec_comirec_backward": (c_int, [POINTER(ComirecShape), _P, _P, _P, _P, _P, _P, c_int64, _P, _P]),
+    "hiprec_comirec_merge": (c_int, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P]),
     "hiprec_vbcar_shape_bytes": (c_size_t, []),
     "hiprec_vbcar_param_floats": (c_int64, [POINTER(VbcarShape)]),
     "hiprec_vbcar_workspace_bytes": (c_size_t, [POINTER(VbcarShape), c_int64, c_int32]),
@@ -980,6 +996,8 @@ def load():
         raise RuntimeError("hiprec_hstu_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_mamba4rec_shape_bytes() != ctypes.sizeof(Mamba4RecShape):
         raise RuntimeError("hiprec_mamba4rec_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_comirec_shape_bytes() != ctypes.sizeof(ComirecShape):
+        raise RuntimeError("hiprec_comirec_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vbcar_shape_bytes() != ctypes.sizeof(VbcarShape):
         raise RuntimeError("hiprec_vbcar_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_tvbr_shape_bytes() != ctypes.sizeof(TvbrShape):

@@ -451,6 +451,39 @@ class SessionLoader:
                    lens.tolist())
 
 
+class MultiInterestLoader:
+    """ComiRec's batches from ``session_prefixes`` output: ``(seq [B, maxlen], target [B], samples [n_sample])`` int64, the
+    prefixes left-padded with 0 (a longer one keeps its last ``maxlen`` items), the samples uniform over ``1 .. n_items``
+    from a seeded generator and shared by the batch.  ``shuffle`` permutes the prefixes anew at every iteration.
+    ``item_probs`` is the sampler's distribution as ``ComiRecEngine.set_item_probs`` takes it."""
+
+    def __init__(self, out_seqs, labels, batch_size, maxlen, n_items, n_sample, shuffle=True, seed=None):
+        if len(out_seqs) != len(labels):
+            raise ValueError("one label per prefix is needed")
+        if int(batch_size) < 1 or int(n_sample) < 1:
+            raise ValueError("batch_size and n_sample must be >= 1")
+        self.batch_size, self.n_items, self.n_sample = int(batch_size), int(n_items), int(n_sample)
+        self._seq = np.zeros((len(out_seqs), int(maxlen)), dtype=np.int64)
+        for r, s in enumerate(out_seqs):
+            s = np.asarray(s, dtype=np.int64)[-int(maxlen):]
+            if s.size:
+                self._seq[r, -s.size:] = s
+        self._labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+        self.shuffle = bool(shuffle)
+        self._rng = np.random.default_rng(seed)
+        self.item_probs = np.concatenate([[0.0], np.full(self.n_items, 1.0 / self.n_items)])
+
+    def __len__(self):
+        return (self._labels.size + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        order = self._rng.permutation(self._labels.size) if self.shuffle else np.arange(self._labels.size)
+        for lo in range(0, order.size, self.batch_size):
+            rows = order[lo:lo + self.batch_size]
+            samples = self._rng.integers(1, self.n_items + 1, self.n_sample)
+            yield torch.from_numpy(self._seq[rows]), torch.from_numpy(self._labels[rows]), torch.from_numpy(samples)
+
+
 # ---- session-parallel mini-batches for GRU4Rec (Hidasi et al., ICLR 2016, section 3.1) -------------------------------------
 class SessionParallelLoader:
     """``batch_size`` slots each walk one session, one event per step; a step is ``(in_items [B], targets [B],

@@ -2092,6 +2092,69 @@ int hiprec_mamba4rec_scan(const float* u, const float* dt_pre, const float* z, c
                           int32_t seq_len, int32_t d_inner, int32_t d_state, float* out, float* du, float* ddt_pre, float* dz,
                           float* dA, float* dBm, float* dCm, float* dD, float* scratch, size_t scratch_floats, void* stream);
 
+/* ================= ComiRec-DR (Cen et al., KDD 2020; MIND's capsule routing, Li et al., CIKM 2019; no counterpart in the
+ * reference: tests/comirec_torch.py is the restatement) ==========================================================
+ * Ids: 0 = padding, 1 .. n_items = items; sequences are [batch, maxlen] int64, left-padded with 0.  D = dim, K = n_interest,
+ * T = maxlen, R = routing_iters.  The parameters live in ONE flat buffer in state_dict() order: item_emb.weight
+ * [n_items + 1, D] (row 0 is zero and receives no gradient), routing.weight [T, K, D, D].  No biases.
+ * Forward, per sequence: e[t] = item_emb[seq[t]]; uh[k, t] = routing.weight[t, k] e[t]; b = 0; R times: c[:, t] =
+ * softmax_k(b[:, t]), 0 at padding; s[k] = sum_t c[k, t] uh[k, t]; n = |s[k]|^2; v[k] = s[k] n / (1 + n) / sqrt(n + 1e-9);
+ * all but the last time b[k, t] += <uh[k, t], v[k]>.  interests = v of the last iteration.  uh is a constant in every
+ * iteration but the last, so the gradient reaches it through the last s only and c is a constant of the backward.
+ * Loss: k* = argmax_k <v[k], E[target]> (lowest k on a tie, no gradient), readout = v[k*]; z_0 = <readout, E[target]>,
+ * z_j = <readout, E[samples[j]]> for the n_sample samples the batch shares; with log_q [n_items + 1] (indexed by id) every
+ * logit is shifted by -log_q[its item]; a sample equal to the row's target is left out of that row; loss = the mean over
+ * the rows with target != 0 of logsumexp(z) - z_0; no such row gives loss 0 and a zero gradient.
+ * Limits: D a multiple of 16 in 16 .. 128, K in 1 .. 8, T in 1 .. 256, R in 1 .. 4, n_sample in 1 .. 8192,
+ * batch * maxlen <= 2^24 and batch <= 65535 * 32. */
+typedef struct hiprec_comirec_shape {
+  int64_t n_items;
+  int32_t dim;
+  int32_t maxlen;
+  int32_t n_interest;
+  int32_t routing_iters;
+} hiprec_comirec_shape;
+size_t hiprec_comirec_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_comirec_param_floats(const hiprec_comirec_shape* shape);
+/* bytes of device workspace a call on [batch, maxlen] with n_sample samples needs (0: unsupported).  Its largest terms are
+ * uh [batch, T, K, D] and the logits [batch, n_sample]; there is no second uh-sized buffer */
+size_t hiprec_comirec_workspace_bytes(const hiprec_comirec_shape* shape, int64_t batch, int32_t n_sample);
+
+/* ---- zero_grad + forward + loss + backward of one training step on seq [batch, maxlen], target [batch] and samples
+ * [n_sample] as a fixed sequence of launches, no host sync.  Accumulates into the dense gradient g_flat (zero on entry, laid
+ * out like w_flat): item_emb.weight receives row atomics (row 0 stays 0), routing.weight plain stores summed in a fixed order
+ * (the same bits on every run).  Leaves the loss partials in scratch and advances the step counter.  interests_out
+ * (optional) [batch, K, D] receives v, kstar_out (optional) [batch] int32 k* (-1 for a row without a label).
+ * g_flat == NULL is the eval forward: only seq is read and interests_out is written.
+ * An id outside [0, n_items] in seq or target, or outside [1, n_items] in samples, sets HIPREC_STATUS_ITEM_OOB; it counts
+ * as padding / as no label / as a zero row and nothing outside the buffers is read or written. */
+int hiprec_comirec_grad(const hiprec_comirec_shape* shape, const float* w_flat, float* g_flat, const int64_t* seq,
+                        const int64_t* target, const int64_t* samples, int64_t batch, int32_t n_sample, const float* log_q,
+                        float* interests_out, int32_t* kstar_out, hiprec_stats* stats, void* scratch, size_t scratch_bytes,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* the stages alone, for the tests and tools/bench_comirec.py.
+ * project: uh [batch, seq_len, K, D] = weight [seq_len, K, D, D] applied to rows[ids[b, t]] (rows [n_rows, D]); a slot is
+ * live when mask[b, t] != 0 (mask given) or ids[b, t] != 0 (mask NULL); live [batch, seq_len] receives that decision, dead
+ * slots give zeros and their row is not read; an id outside [0, n_rows) sets the status word. */
+int hiprec_comirec_project(const float* weight, const float* rows, int64_t n_rows, const int64_t* ids, const uint8_t* mask,
+                           int64_t batch, int32_t seq_len, int32_t n_interest, int32_t dim, float* uh, uint8_t* live,
+                           hiprec_stats* stats, void* stream);
+/* route: `iters` routing iterations on uh and live: interests [batch, K, D], c [batch, K, seq_len] and nsq [batch, K] (|s|^2)
+ * of the last iteration */
+int hiprec_comirec_route(const float* uh, const uint8_t* live, int64_t batch, int32_t seq_len, int32_t n_interest,
+                         int32_t dim, int32_t iters, float* interests, float* c, float* nsq, void* stream);
+/* backward: from ds [batch, D] (the gradient of s[k*]), kstar [batch] (-1: none) and c [batch, K, maxlen] the gradient of
+ * routing.weight (stores) and of item_emb.weight through e (row atomics) into g_flat; lists: 8 + K * batch int32 of scratch */
+int hiprec_comirec_backward(const hiprec_comirec_shape* shape, const float* w_flat, float* g_flat, const int64_t* seq,
+                            const float* c, const float* ds, const int32_t* kstar, int64_t batch, int32_t* lists,
+                            void* stream);
+/* merge: items / scores [n * n_interest, k] as hiprec_topk_recommend leaves them for the n_interest rows of each of n
+ * sequences -> per sequence the k best DISTINCT items by their highest score, ties to the lower id, -1 / -inf in a tail */
+int hiprec_comirec_merge(const int64_t* items, const float* scores, int64_t n, int32_t n_interest, int32_t k,
+                         int64_t* out_items, float* out_scores, void* stream);
+
 /* ================= VBCAR (beta_rec/models/vbcar.py) ================================================
  * The parameters live in ONE flat buffer in state_dict() order: user_emb [n_users, emb_dim], item_emb [n_items, emb_dim],
  * fc_u_1_mu.weight [late_dim, fea_u], .bias [late_dim], fc_u_2_mu.weight [2 emb_dim, late_dim], .bias [2 emb_dim], then
