@@ -26,6 +26,7 @@ STATUS_TABLE_FULL = 64
 STATUS_TIME_OOB = 128
 STATUS_NOT_SPD = 256
 STATUS_NOT_FINITE = 512
+STATUS_BATCH_STATS = 1024
 
 
 class MfTables(Structure):
@@ -291,6 +292,13 @@ class ComirecShape(Structure):
 
     _fields_ = [("n_items", c_int64), ("dim", c_int32), ("maxlen", c_int32), ("n_interest", c_int32),
                 ("routing_iters", c_int32)]
+
+
+class DinShape(Structure):
+    """hiprec_din_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_items", c_int64), ("dim", c_int32), ("maxlen", c_int32), ("att_h1", c_int32), ("att_h2", c_int32),
+                ("att_act", c_int32), ("dnn_act", c_int32), ("n_dnn", c_int32), ("dnn", c_int32 * 3)]
 
 
 class HstuShape(Structure):
@@ -732,6 +740,14 @@ SIGNATURES = {
     "hiprec_vbcar_shape_bytes": (c_size_t, []),
     "hiprec_vbcar_param_floats": (c_int64, [POINTER(VbcarShape)]),
     "hiprec_vbcar_workspace_bytes": (c_size_t, [POINTER(VbcarShape), c_int64, c_int32]),
+    "hiprec_din_shape_bytes": (c_size_t, []),
+    "hiprec_din_param_floats": (c_int64, [POINTER(DinShape)]),
+    "hiprec_din_tiles": (c_int, [POINTER(DinShape), POINTER(c_int32)]),
+    "hiprec_din_workspace_bytes": (c_size_t, [POINTER(DinShape), c_int64, c_int64, c_int32]),
+    "hiprec_din_grad": (
+        c_int, [POINTER(DinShape), _P, _P, _P, c_int32, _P, _P, _P, c_int64, c_int64, _P, _P, _P, c_size_t, _P, c_size_t, _P]),
+    "hiprec_din_attention": (
+        c_int, [POINTER(DinShape), _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "hiprec_vbcar_encode_workspace_bytes": (c_size_t, [POINTER(VbcarShape), c_int64, c_int32]),
     "hiprec_vbcar_grad": (
         c_int,
@@ -998,6 +1014,8 @@ def load():
         raise RuntimeError("hiprec_mamba4rec_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_comirec_shape_bytes() != ctypes.sizeof(ComirecShape):
         raise RuntimeError("hiprec_comirec_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_din_shape_bytes() != ctypes.sizeof(DinShape):
+        raise RuntimeError("hiprec_din_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vbcar_shape_bytes() != ctypes.sizeof(VbcarShape):
         raise RuntimeError("hiprec_vbcar_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_tvbr_shape_bytes() != ctypes.sizeof(TvbrShape):

@@ -45,6 +45,8 @@ def raise_on_status(status):
             which.append("time step")
         if status & _lib.STATUS_NEG_EXHAUSTED:
             raise ValueError("Sample larger than population or is negative")  # random.sample's message
+        if status & _lib.STATUS_BATCH_STATS:
+            raise ValueError("Expected more than 1 value per channel when training (Dice: one live candidate)")
         if status & _lib.STATUS_LAZY_TABLE:
             raise RuntimeError(
                 "lazy Adam: the optimizer ran past the bias-correction table while the corrections still moved "

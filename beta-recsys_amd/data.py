@@ -484,6 +484,46 @@ class MultiInterestLoader:
             yield torch.from_numpy(self._seq[rows]), torch.from_numpy(self._labels[rows]), torch.from_numpy(samples)
 
 
+class CandidateLoader:
+    """DIN's batches from ``session_prefixes`` output: ``(seq [B, maxlen], cand [B, 1 + n_neg], label [B, 1 + n_neg])``, the
+    prefixes left-padded with 0 (a longer one keeps its last ``maxlen`` items), the target in column 0 with label 1 and
+    ``n_neg`` negatives uniform over ``1 .. n_items`` and different from it with label 0.  Seeded; ``shuffle`` permutes the
+    prefixes anew at every iteration, and the negatives are redrawn."""
+
+    def __init__(self, out_seqs, labels, batch_size, maxlen, n_items, n_neg, shuffle=True, seed=None):
+        if len(out_seqs) != len(labels):
+            raise ValueError("one label per prefix is needed")
+        if int(batch_size) < 1 or int(n_neg) < 0 or int(n_items) < 2:
+            raise ValueError("batch_size >= 1, n_neg >= 0 and n_items >= 2 are needed")
+        self.batch_size, self.n_items, self.n_neg = int(batch_size), int(n_items), int(n_neg)
+        self._seq = np.zeros((len(out_seqs), int(maxlen)), dtype=np.int64)
+        for r, s in enumerate(out_seqs):
+            s = np.asarray(s, dtype=np.int64)[-int(maxlen):]
+            if s.size:
+                self._seq[r, -s.size:] = s
+        self._labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+        self.shuffle = bool(shuffle)
+        self._rng = np.random.default_rng(seed)
+
+    def __len__(self):
+        return (self._labels.size + self.batch_size - 1) // self.batch_size
+
+    def candidates(self, targets):
+        """``[n, 1 + n_neg]``: the target, then negatives drawn from the ``n_items - 1`` other items."""
+        targets = np.asarray(targets, dtype=np.int64).reshape(-1, 1)
+        neg = self._rng.integers(1, self.n_items, (targets.shape[0], self.n_neg))
+        return np.concatenate([targets, neg + (neg >= targets)], axis=1)
+
+    def __iter__(self):
+        order = self._rng.permutation(self._labels.size) if self.shuffle else np.arange(self._labels.size)
+        label = np.zeros((self.batch_size, 1 + self.n_neg), dtype=np.float32)
+        label[:, 0] = 1.0
+        for lo in range(0, order.size, self.batch_size):
+            rows = order[lo:lo + self.batch_size]
+            yield (torch.from_numpy(self._seq[rows]), torch.from_numpy(self.candidates(self._labels[rows])),
+                   torch.from_numpy(label[:rows.size].copy()))
+
+
 # ---- session-parallel mini-batches for GRU4Rec (Hidasi et al., ICLR 2016, section 3.1) -------------------------------------
 class SessionParallelLoader:
     """``batch_size`` slots each walk one session, one event per step; a step is ``(in_items [B], targets [B],

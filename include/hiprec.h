@@ -2155,6 +2155,66 @@ int hiprec_comirec_backward(const hiprec_comirec_shape* shape, const float* w_fl
 int hiprec_comirec_merge(const int64_t* items, const float* scores, int64_t n, int32_t n_interest, int32_t k,
                          int64_t* out_items, float* out_scores, void* stream);
 
+/* ================= DIN (Deep Interest Network, Zhou et al., KDD 2018; no counterpart in the reference: tests/din_torch.py
+ * is the restatement) ====================================================================================================
+ * A ranking model: the history is re-read for every candidate.  Ids: 0 = padding / a dead candidate slot, 1 .. n_items =
+ * items; seq [batch, maxlen] int64 left-padded with 0, cand [batch, n_cand] int64, label [batch, n_cand] fp32.
+ * D = dim, T = maxlen, H1 / H2 = att_h1 / att_h2, W_l = dnn[l].  The parameters live in ONE flat buffer in state_dict()
+ * order: item_emb.weight [n_items + 1, D] (row 0 is zero and receives no gradient); att.0.weight [H1, 4 D], att.0.bias,
+ * att.0.alpha [H1]; att.1.weight [H2, H1], att.1.bias, att.1.alpha [H2]; att.2.weight [1, H2], att.2.bias [1]; for every
+ * tower layer dnn.l.weight [W_l, in_l], dnn.l.bias, dnn.l.alpha [W_l] (in_0 = 3 D); out.weight [1, W_last], out.bias [1].
+ * The alphas of the unit are read by att_act = prelu only (and get a zero gradient otherwise).  Dice's running buffers are a
+ * second buffer `running`: per tower layer running_mean [W_l], then running_var [W_l].
+ * Forward per (sequence, candidate): e_t = E[seq[t]], q = E[cand]; h1 = act(att.0 [q, e_t, q - e_t, q * e_t]),
+ * h2 = act(att.1 h1), a_t = (att.2 h2) / sqrt(D), 0 at padding (no softmax); pooled = sum_t a_t e_t; z = [pooled, q,
+ * pooled * q]; every tower layer is Linear + Dice (dnn_act 0: y = x (alpha + p (1 - alpha)), p = sigmoid(BN(x)), BN =
+ * BatchNorm1d(eps 1e-8, affine False, momentum 0.1) over the live candidate rows) or PReLU (dnn_act 1); logit = out(y).
+ * Loss: BCE-with-logits, the mean over the live candidates (cand != 0); none gives loss 0 and a zero gradient.
+ * Limits: D a multiple of 16 in 16 .. 128, T in 1 .. 256, H1 and H2 in 1 .. 128, 1 .. 3 tower widths in 1 .. 512,
+ * batch * maxlen <= 2^24 and batch * n_cand <= 2^24. */
+#define HIPREC_STATUS_BATCH_STATS 1024u /* DIN: a Dice training batch with exactly one live candidate has no variance */
+typedef struct hiprec_din_shape {
+  int64_t n_items;
+  int32_t dim;
+  int32_t maxlen;
+  int32_t att_h1;
+  int32_t att_h2;
+  int32_t att_act; /* 0 sigmoid, 1 prelu */
+  int32_t dnn_act; /* 0 dice, 1 prelu */
+  int32_t n_dnn;
+  int32_t dnn[3];
+} hiprec_din_shape;
+size_t hiprec_din_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_din_param_floats(const hiprec_din_shape* shape);
+/* out[7]: positions of an MFMA tile, of a staged chunk in the forward and in the backward (64 / 32 / 16: the largest that fits
+ * the 160 KB of LDS and is not longer than needed), candidates of a forward workgroup, slabs of the weight-gradient fold,
+ * and what is resident in LDS forward / backward (bit 0: Wp, bit 1: att.1.weight; the rest is read through L2) */
+int hiprec_din_tiles(const hiprec_din_shape* shape, int32_t* out);
+/* bytes of device workspace of a call (0: unsupported); train != 0 includes the backward's buffers.  Nothing in it is
+ * [batch, n_cand, maxlen, width]: the largest terms are U [batch maxlen, H1] and the tower's [batch n_cand, W_l] */
+size_t hiprec_din_workspace_bytes(const hiprec_din_shape* shape, int64_t batch, int64_t n_cand, int32_t train);
+
+/* ---- zero_grad + forward + loss + backward of one training step as a fixed sequence of launches, no host sync.  Writes
+ * the dense gradient g_flat (zero on entry, laid out like w_flat): item_emb.weight receives row atomics (row 0 stays 0),
+ * everything else plain stores summed in a fixed order (the same bits on every run).  Leaves the loss partials in scratch
+ * and advances the step counter.  update_running != 0 moves Dice's running buffers as BatchNorm1d does.  logits_out
+ * (optional when training) [batch, n_cand] receives the logits, 0 in dead slots.
+ * g_flat == NULL is the eval forward: Dice reads the running buffers, label is not read, logits_out is written.
+ * An id outside [0, n_items] sets HIPREC_STATUS_ITEM_OOB and counts as padding / as a dead slot; nothing outside the
+ * buffers is read or written.  A Dice training batch with one live candidate sets HIPREC_STATUS_BATCH_STATS. */
+int hiprec_din_grad(const hiprec_din_shape* shape, const float* w_flat, float* g_flat, float* running,
+                    int32_t update_running, const int64_t* seq, const int64_t* cand, const float* label, int64_t batch,
+                    int64_t n_cand, float* logits_out, hiprec_stats* stats, void* scratch, size_t scratch_bytes,
+                    void* workspace, size_t workspace_bytes, void* stream);
+/* the activation-unit stage alone on explicit rows e [batch, maxlen, D], q_rows [batch, n_cand, D] and mask [batch, maxlen]
+ * (any pattern): pooled [batch, n_cand, D] and a [batch, n_cand, maxlen], exactly 0 where the mask is.  With dpooled
+ * [batch, n_cand, D] also its backward: the gradients of att.0.weight .. att.2.bias into g_att (zero on entry, laid out like that
+ * span of the flat buffer), de [batch, maxlen, D] and dq [batch, n_cand, D]. */
+int hiprec_din_attention(const hiprec_din_shape* shape, const float* w_flat, const float* e, const float* q_rows,
+                         const uint8_t* mask, int64_t batch, int64_t n_cand, float* pooled, float* a, const float* dpooled,
+                         float* g_att, float* de, float* dq, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ================= VBCAR (beta_rec/models/vbcar.py) ================================================
  * The parameters live in ONE flat buffer in state_dict() order: user_emb [n_users, emb_dim], item_emb [n_items, emb_dim],
  * fc_u_1_mu.weight [late_dim, fea_u], .bias [late_dim], fc_u_2_mu.weight [2 emb_dim, late_dim], .bias [2 emb_dim], then
