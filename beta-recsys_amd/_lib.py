@@ -301,6 +301,13 @@ class DinShape(Structure):
                 ("att_act", c_int32), ("dnn_act", c_int32), ("n_dnn", c_int32), ("dnn", c_int32 * 3)]
 
 
+class DienShape(Structure):
+    """hiprec_dien_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_items", c_int64), ("dim", c_int32), ("maxlen", c_int32), ("dnn_act", c_int32), ("n_dnn", c_int32),
+                ("dnn", c_int32 * 3), ("aux_weight", c_float)]
+
+
 class HstuShape(Structure):
     """hiprec_hstu_shape (include/hiprec.h)."""
 
@@ -748,6 +755,17 @@ SIGNATURES = {
         c_int, [POINTER(DinShape), _P, _P, _P, c_int32, _P, _P, _P, c_int64, c_int64, _P, _P, _P, c_size_t, _P, c_size_t, _P]),
     "hiprec_din_attention": (
         c_int, [POINTER(DinShape), _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "hiprec_dien_shape_bytes": (c_size_t, []),
+    "hiprec_dien_param_floats": (c_int64, [POINTER(DienShape)]),
+    "hiprec_dien_tiles": (c_int, [POINTER(DienShape), c_int64, POINTER(c_int32)]),
+    "hiprec_dien_workspace_bytes": (c_size_t, [POINTER(DienShape), c_int64, c_int64, c_int32]),
+    "hiprec_dien_grad": (
+        c_int, [POINTER(DienShape), _P, _P, _P, c_int32, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, c_size_t, _P, c_size_t,
+                _P]),
+    "hiprec_dien_score": (c_int, [POINTER(DienShape), _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
+    "hiprec_dien_evolve": (
+        c_int, [POINTER(DienShape), _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "hiprec_dien_extract": (c_int, [POINTER(DienShape), _P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),
     "hiprec_vbcar_encode_workspace_bytes": (c_size_t, [POINTER(VbcarShape), c_int64, c_int32]),
     "hiprec_vbcar_grad": (
         c_int,
@@ -1016,6 +1034,8 @@ def load():
         raise RuntimeError("hiprec_comirec_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_din_shape_bytes() != ctypes.sizeof(DinShape):
         raise RuntimeError("hiprec_din_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_dien_shape_bytes() != ctypes.sizeof(DienShape):
+        raise RuntimeError("hiprec_dien_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vbcar_shape_bytes() != ctypes.sizeof(VbcarShape):
         raise RuntimeError("hiprec_vbcar_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_tvbr_shape_bytes() != ctypes.sizeof(TvbrShape):

@@ -30,13 +30,12 @@
 // The only float atomics are rows of d item_emb.weight; every other gradient is the same bits on every run.
 #include <algorithm>
 
-#include "gemm.hpp"
-#include "seqrec.hpp"
+#include "din.hpp"
 
 namespace hiprec {
 namespace {
 
-constexpr int kDinMaxDim = 128, kDinMaxLen = 256, kDinMaxAtt = 128, kDinMaxDnn = 512, kDinMaxLayers = 3;
+constexpr int kDinMaxAtt = 128;
 constexpr int kDinTile = 16;                   // positions of a wave's MFMA tile
 constexpr int kDinMaxChunk = 64;               // staged positions: one tile per wave
 constexpr int kDinSlice = 4;                   // forward: candidates of a workgroup
@@ -44,9 +43,7 @@ constexpr int kDinSlabs = 256;                 // backward: workgroups, each wit
 constexpr int kDinColTiles = kDinMaxAtt / 16;  // column tiles a wave walks per product
 constexpr int kDinWTiles = kDinColTiles * kDinColTiles / kWavesPerBlock;   // weight-gradient tiles of a wave
 constexpr int kDinSplitE = 8, kDinSplitQ = 3;  // K-slices of the two folded-weight gradient GEMMs (one grouped launch)
-constexpr int kDinSplitRows = 256;             // ... each at least this long
 constexpr size_t kDinLdsBudget = 160 * 1024;
-constexpr int64_t kDinMaxRows = 1ll << 24;     // B T and B C
 constexpr float kDiceEps = 1e-8f, kDiceMomentum = 0.1f;
 constexpr int kColW = 16, kColG = 16;          // column kernels: columns and row groups of a block
 constexpr int kColFly = 8;                     // ... rows a thread has in flight
@@ -567,19 +564,6 @@ struct DinUnfold {
   float *a0w, *a0a, *a1w, *a1b, *a1a, *a2w, *a2b;
   int n_slabs, D, H1, H2, n_e, n_q;      // n_e / n_q: K-slices of d (We - Wd) / d (Wq + Wd), each [H1, D]
 };
-// element `at` summed over n parts `stride` apart: eight running sums (part k into sum k % 8, so that eight loads are in
-// flight at a time), folded as a tree.  The association depends on n alone: the same bits on every run.
-__device__ __forceinline__ float din_slab_sum(const float* slabs, int n, int64_t stride, int64_t at) {
-  float p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int k = 0; k < n; k += 8) {
-    float v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = k + i < n ? slabs[(k + i) * stride + at] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) p[i] += v[i];
-  }
-  return ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-}
 __global__ __launch_bounds__(kBlock) void din_unfold_kernel(DinUnfold p) {
   const DinSlab o = din_slab(p.D, p.H1, p.H2);
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
@@ -811,6 +795,147 @@ __global__ __launch_bounds__(kBlock) void din_mask_logits_kernel(float* __restri
     if (!live[i]) logit[i] = 0.f;
 }
 
+}  // namespace
+
+// ---- what csrc/dien.hip shares (din.hpp) ----------------------------------------------------------------------------------
+int din_gather(const float* E, int64_t n_items, int D, const int64_t* seq, const int64_t* cand, int64_t BT, int64_t N,
+               float* rows, float* q, uint8_t* lv, uint8_t* lc, hiprec_stats* stats, hipStream_t st) {
+  din_gather_kernel<<<grid_for_waves(BT + N), kBlock, 0, st>>>(E, n_items, D, seq, cand, BT, N, rows, q, lv, lc, stats);
+  HIPREC_TRY(hipGetLastError());
+  return 0;
+}
+int din_flags(const uint8_t* mask, uint8_t* lv, int64_t BT, uint8_t* lc, int64_t N, hipStream_t st) {
+  din_flags_kernel<<<grid_for_threads(BT + N), kBlock, 0, st>>>(mask, lv, BT, lc, N);
+  HIPREC_TRY(hipGetLastError());
+  return 0;
+}
+int din_scatter(const float* drows, const float* dqa, const float* dqb, const int64_t* seq, const int64_t* cand,
+                const uint8_t* lv, const uint8_t* lc, int64_t BT, int64_t N, int D, float* g_item, hipStream_t st) {
+  din_scatter_kernel<<<grid_for_waves(BT + N), kBlock, 0, st>>>(drows, dqa, dqb, seq, cand, lv, lc, BT, N, D, g_item);
+  HIPREC_TRY(hipGetLastError());
+  return 0;
+}
+int din_fill(float* p, int64_t n, float v, hipStream_t st) {
+  din_fill_kernel<<<grid_for_threads(n), kBlock, 0, st>>>(p, n, v);
+  HIPREC_TRY(hipGetLastError());
+  return 0;
+}
+int din_add(float* dst, const float* src, int64_t n, hipStream_t st) {
+  din_add_kernel<<<grid_for_threads(n), kBlock, 0, st>>>(dst, src, n);
+  HIPREC_TRY(hipGetLastError());
+  return 0;
+}
+int din_z(const float* v, const float* q, int64_t N, int D, float* z, hipStream_t st) {
+  din_z_kernel<<<grid_for_threads(N * D), kBlock, 0, st>>>(v, q, N, D, z);
+  HIPREC_TRY(hipGetLastError());
+  return 0;
+}
+int din_z_bwd(const float* dz, const float* v, const float* q, int64_t N, int D, float* dv, float* dq, hipStream_t st) {
+  din_z_bwd_kernel<<<grid_for_threads(N * D), kBlock, 0, st>>>(dz, v, q, N, D, dv, dq);
+  HIPREC_TRY(hipGetLastError());
+  return 0;
+}
+
+int din_tower_forward(const DinTower& t, const float* w_flat, float* bn, int update_running, bool train, const float* z,
+                      const uint8_t* lc, int64_t N, float* logits_out, hiprec_stats* stats, hipStream_t st) {
+  const int Ni = static_cast<int>(N);
+  const float* in = z;
+  int moff = 0;
+  for (int l = 0; l < t.L; ++l) {
+    const int W = t.W[l];
+    GemmGroup g{};
+    g.n = 1;
+    g.p[0] = make_gemm(kNT, Ni, W, t.in[l], in, t.in[l], w_flat + t.dw[l], t.in[l], t.x[l], W, w_flat + t.db[l], 0, nullptr, 0,
+                       false);
+    if (int rc = launch_group(g, st)) return rc;
+    const float *mean = t.mean + moff, *var = t.var + moff;
+    if (t.act == 0) {
+      if (train) {
+        din_bn_stats_kernel<<<(W + kColW - 1) / kColW, kBlock, 0, st>>>(t.x[l], lc, N, W, t.mean + moff, t.var + moff,
+                                                                        update_running ? bn + t.bn[l] : nullptr, stats);
+        HIPREC_TRY(hipGetLastError());
+      } else {
+        mean = bn + t.bn[l];
+        var = bn + t.bn[l] + W;
+      }
+    }
+    din_act_fwd_kernel<<<grid_for_threads(N * W), kBlock, 0, st>>>(t.x[l], mean, var, w_flat + t.da[l], N, W, t.act, t.y[l]);
+    HIPREC_TRY(hipGetLastError());
+    in = t.y[l];
+    moff += W;
+  }
+  const int WL = t.W[t.L - 1];
+  float* logit = train ? t.logit : logits_out;
+  GemmGroup g{};
+  g.n = 1;
+  g.p[0] = make_gemm(kNT, Ni, 1, WL, in, WL, w_flat + t.ow, WL, logit, 1, w_flat + t.ob, 0, nullptr, 0, false);
+  if (int rc = launch_group(g, st)) return rc;
+  if (!train) {
+    din_mask_logits_kernel<<<grid_for_threads(N), kBlock, 0, st>>>(logit, lc, N);
+    HIPREC_TRY(hipGetLastError());
+  }
+  return 0;
+}
+
+int din_tower_backward(const DinTower& t, const float* w_flat, float* g_flat, const float* z, const uint8_t* lc,
+                       const float* label, int64_t N, float* logits_out, Scratch* scratch, hiprec_stats* stats,
+                       hipStream_t st, float** dz) {
+  const int Ni = static_cast<int>(N), WL = t.W[t.L - 1];
+  const float* in = t.y[t.L - 1];
+  int moff = 0;
+  for (int l = 0; l < t.L; ++l) moff += t.W[l];
+  din_bce_kernel<<<grid_for_threads(N), kBlock, 0, st>>>(t.logit, label, lc, N, t.dlogit, scratch, stats);
+  HIPREC_TRY(hipGetLastError());
+  if (logits_out) HIPREC_TRY(hipMemcpyAsync(logits_out, t.logit, sizeof(float) * N, hipMemcpyDeviceToDevice, st));
+  // the output layer: d y_L = d logit out.weight, d out.weight = d logit^T y_L, d out.bias = sum d logit
+  float *dcur = t.dA, *dnext = t.dB;
+  {
+    GemmGroup g{};
+    g.n = 3;
+    g.p[0] = make_gemm(kNN, Ni, WL, 1, t.dlogit, 1, w_flat + t.ow, WL, dcur, WL, nullptr, 0, nullptr, 0, false);
+    g.p[1] = make_gemm(kTNm, 1, WL, Ni, t.dlogit, 1, in, WL, g_flat + t.ow, WL, nullptr, 0, nullptr, 0, false);
+    g.p[2] = make_colsum(t.dlogit, Ni, 1, 1, g_flat + t.ob, t.cs);
+    if (int rc = launch_group(g, st)) return rc;
+    if (int rc = launch_colsum_reduce(g, st)) return rc;
+  }
+  for (int l = t.L - 1; l >= 0; --l) {
+    const int W = t.W[l], K = t.in[l];
+    moff -= W;
+    const float* lin = l ? t.y[l - 1] : z;
+    din_act_bwd_stats_kernel<<<(W + kColW - 1) / kColW, kBlock, 0, st>>>(t.x[l], dcur, t.mean + moff, t.var + moff,
+                                                                         w_flat + t.da[l], lc, N, W, t.act, t.sums,
+                                                                         g_flat + t.da[l]);
+    HIPREC_TRY(hipGetLastError());
+    din_act_bwd_kernel<<<grid_for_threads(N * W), kBlock, 0, st>>>(t.x[l], dcur, t.mean + moff, t.var + moff, w_flat + t.da[l],
+                                                                   lc, t.sums, N, W, t.act);
+    HIPREC_TRY(hipGetLastError());
+    GemmGroup g{};
+    g.n = 3;
+    g.p[0] = make_gemm(kNN, Ni, K, W, dcur, W, w_flat + t.dw[l], K, dnext, K, nullptr, 0, nullptr, 0, false);
+    g.p[1] = make_gemm(kTNm, W, K, Ni, dcur, W, lin, K, g_flat + t.dw[l], K, nullptr, 0, nullptr, 0, false);
+    g.p[2] = make_colsum(dcur, Ni, W, W, g_flat + t.db[l], t.cs);
+    if (int rc = launch_group(g, st)) return rc;
+    if (int rc = launch_colsum_reduce(g, st)) return rc;
+    std::swap(dcur, dnext);
+  }
+  *dz = dcur;
+  return 0;
+}
+
+int din_add_wgrad_slices(GemmGroup& g, int want, int M, int N, int K, const float* A, int lda, const float* Bm, int ldb,
+                         float* parts) {
+  const int n = std::max(1, std::min(want, K / kDinSplitRows));
+  const int len = ((K + n - 1) / n + 3) / 4 * 4;
+  for (int i = 0; i < n; ++i) {
+    const int k0 = i * len, kn = std::min(len, K - k0);
+    g.p[g.n++] = make_gemm(kTNm, M, N, kn, A + static_cast<int64_t>(k0) * lda, lda, Bm + static_cast<int64_t>(k0) * ldb, ldb,
+                           parts + static_cast<int64_t>(i) * M * N, N, nullptr, 0, nullptr, 0, false);
+  }
+  return n;
+}
+
+namespace {
+
 // ---- host side ----------------------------------------------------------------------------------------------------------
 int din_check_shape(const hiprec_din_shape* s) {
   HIPREC_REQUIRE(s, "NULL shape");
@@ -949,20 +1074,6 @@ int din_unit_forward(const DinDims& q, const DinOff& o, const float* w_flat, con
   return 0;
 }
 
-// C_i [M, N] = A[k_i .. k_i+1)^T B[k_i .. k_i+1) for up to `want` K-slices of at least kDinSplitRows rows: problems of the
-// caller's grouped launch, each a block per tile with plain stores; din_unfold_kernel adds the slices in order
-int din_add_wgrad_slices(GemmGroup& g, int want, int M, int N, int K, const float* A, int lda, const float* Bm, int ldb,
-                         float* parts) {
-  const int n = std::max(1, std::min(want, K / kDinSplitRows));
-  const int len = ((K + n - 1) / n + 3) / 4 * 4;
-  for (int i = 0; i < n; ++i) {
-    const int k0 = i * len, kn = std::min(len, K - k0);
-    g.p[g.n++] = make_gemm(kTNm, M, N, kn, A + static_cast<int64_t>(k0) * lda, lda, Bm + static_cast<int64_t>(k0) * ldb, ldb,
-                           parts + static_cast<int64_t>(i) * M * N, N, nullptr, 0, nullptr, 0, false);
-  }
-  return n;
-}
-
 // After the fused backward: d (We - Wd), d (Wq + Wd), d att.0.bias and the rows d U (We - Wd), d V (Wq + Wd) in one grouped
 // launch, then the fold of the slabs and slices into the unit's gradients, which start at g_att (att.0.weight)
 int din_unit_finish(const DinDims& q, const DinOff& o, const DinWs& a, int64_t BT, int64_t N, int n_slabs, float* g_att,
@@ -985,6 +1096,17 @@ int din_unit_finish(const DinDims& q, const DinOff& o, const DinWs& a, int64_t B
   return 0;
 }
 
+DinTower din_tower_of(const DinDims& q, const DinOff& o, const DinWs& a) {
+  DinTower t{};
+  t.L = q.L; t.act = q.dnn_act; t.ow = o.ow; t.ob = o.ob;
+  for (int l = 0; l < q.L; ++l) {
+    t.W[l] = q.W[l]; t.in[l] = o.in[l]; t.bn[l] = o.bn[l]; t.dw[l] = o.dw[l]; t.db[l] = o.db[l]; t.da[l] = o.da[l];
+    t.x[l] = a.x[l]; t.y[l] = a.y[l];
+  }
+  t.mean = a.mean; t.var = a.var; t.logit = a.logit; t.dlogit = a.dlogit; t.dA = a.dA; t.dB = a.dB; t.sums = a.sums; t.cs = a.cs;
+  return t;
+}
+
 int din_run(const DinDims& q, const float* w_flat, float* g_flat, float* bn, int update_running, const int64_t* seq,
             const int64_t* cand, const float* label, int64_t B, int64_t C, float* logits_out, hiprec_stats* stats,
             Scratch* scratch, float* ws_base, hipStream_t st) {
@@ -992,93 +1114,19 @@ int din_run(const DinDims& q, const float* w_flat, float* g_flat, float* bn, int
   const DinOff o = din_offsets(q);
   const DinWs a = din_carve_ws(ws_base, q, B, C, train);
   const int64_t BT = B * q.T, N = B * C;
-  const int Ni = static_cast<int>(N), D = q.D;
+  const int D = q.D;
   if (int rc = din_prep(q, o, w_flat, a, st)) return rc;
-  din_gather_kernel<<<grid_for_waves(BT + N), kBlock, 0, st>>>(w_flat, q.n_items, D, seq, cand, BT, N, a.rows, a.q, a.lv,
-                                                               a.lc, stats);
-  HIPREC_TRY(hipGetLastError());
+  if (int rc = din_gather(w_flat, q.n_items, D, seq, cand, BT, N, a.rows, a.q, a.lv, a.lc, stats, st)) return rc;
   if (int rc = din_unit_forward(q, o, w_flat, a, B, C, a.pooled, a.a, st)) return rc;
-  din_z_kernel<<<grid_for_threads(N * D), kBlock, 0, st>>>(a.pooled, a.q, N, D, a.z);
-  HIPREC_TRY(hipGetLastError());
+  if (int rc = din_z(a.pooled, a.q, N, D, a.z, st)) return rc;
 
-  const float* in = a.z;
-  int moff = 0;
-  for (int l = 0; l < q.L; ++l) {
-    const int W = q.W[l];
-    GemmGroup g{};
-    g.n = 1;
-    g.p[0] = make_gemm(kNT, Ni, W, o.in[l], in, o.in[l], w_flat + o.dw[l], o.in[l], a.x[l], W, w_flat + o.db[l], 0, nullptr, 0,
-                       false);
-    if (int rc = launch_group(g, st)) return rc;
-    const float *mean = a.mean + moff, *var = a.var + moff;
-    if (q.dnn_act == 0) {
-      if (train) {
-        din_bn_stats_kernel<<<(W + kColW - 1) / kColW, kBlock, 0, st>>>(a.x[l], a.lc, N, W, a.mean + moff, a.var + moff,
-                                                                        update_running ? bn + o.bn[l] : nullptr, stats);
-        HIPREC_TRY(hipGetLastError());
-      } else {
-        mean = bn + o.bn[l];
-        var = bn + o.bn[l] + W;
-      }
-    }
-    din_act_fwd_kernel<<<grid_for_threads(N * W), kBlock, 0, st>>>(a.x[l], mean, var, w_flat + o.da[l], N, W, q.dnn_act,
-                                                                   a.y[l]);
-    HIPREC_TRY(hipGetLastError());
-    in = a.y[l];
-    moff += W;
-  }
-  const int WL = q.W[q.L - 1];
-  float* logit = train ? a.logit : logits_out;
-  {
-    GemmGroup g{};
-    g.n = 1;
-    g.p[0] = make_gemm(kNT, Ni, 1, WL, in, WL, w_flat + o.ow, WL, logit, 1, w_flat + o.ob, 0, nullptr, 0, false);
-    if (int rc = launch_group(g, st)) return rc;
-  }
-  if (!train) {
-    din_mask_logits_kernel<<<grid_for_threads(N), kBlock, 0, st>>>(logit, a.lc, N);
-    HIPREC_TRY(hipGetLastError());
-    return 0;
-  }
-
-  din_bce_kernel<<<grid_for_threads(N), kBlock, 0, st>>>(a.logit, label, a.lc, N, a.dlogit, scratch, stats);
-  HIPREC_TRY(hipGetLastError());
-  if (logits_out) HIPREC_TRY(hipMemcpyAsync(logits_out, a.logit, sizeof(float) * N, hipMemcpyDeviceToDevice, st));
-  // the output layer: d y_L = d logit out.weight, d out.weight = d logit^T y_L, d out.bias = sum d logit
-  float *dcur = a.dA, *dnext = a.dB;
-  {
-    GemmGroup g{};
-    g.n = 3;
-    g.p[0] = make_gemm(kNN, Ni, WL, 1, a.dlogit, 1, w_flat + o.ow, WL, dcur, WL, nullptr, 0, nullptr, 0, false);
-    g.p[1] = make_gemm(kTNm, 1, WL, Ni, a.dlogit, 1, in, WL, g_flat + o.ow, WL, nullptr, 0, nullptr, 0, false);
-    g.p[2] = make_colsum(a.dlogit, Ni, 1, 1, g_flat + o.ob, a.cs);
-    if (int rc = launch_group(g, st)) return rc;
-    if (int rc = launch_colsum_reduce(g, st)) return rc;
-  }
-  for (int l = q.L - 1; l >= 0; --l) {
-    const int W = q.W[l], K = o.in[l];
-    moff -= W;
-    const float* lin = l ? a.y[l - 1] : a.z;
-    din_act_bwd_stats_kernel<<<(W + kColW - 1) / kColW, kBlock, 0, st>>>(a.x[l], dcur, a.mean + moff, a.var + moff,
-                                                                         w_flat + o.da[l], a.lc, N, W, q.dnn_act, a.sums,
-                                                                         g_flat + o.da[l]);
-    HIPREC_TRY(hipGetLastError());
-    din_act_bwd_kernel<<<grid_for_threads(N * W), kBlock, 0, st>>>(a.x[l], dcur, a.mean + moff, a.var + moff, w_flat + o.da[l],
-                                                                   a.lc, a.sums, N, W, q.dnn_act);
-    HIPREC_TRY(hipGetLastError());
-    GemmGroup g{};
-    g.n = 3;
-    g.p[0] = make_gemm(kNN, Ni, K, W, dcur, W, w_flat + o.dw[l], K, dnext, K, nullptr, 0, nullptr, 0, false);
-    g.p[1] = make_gemm(kTNm, W, K, Ni, dcur, W, lin, K, g_flat + o.dw[l], K, nullptr, 0, nullptr, 0, false);
-    g.p[2] = make_colsum(dcur, Ni, W, W, g_flat + o.db[l], a.cs);
-    if (int rc = launch_group(g, st)) return rc;
-    if (int rc = launch_colsum_reduce(g, st)) return rc;
-    std::swap(dcur, dnext);
-  }
-  din_z_bwd_kernel<<<grid_for_threads(N * D), kBlock, 0, st>>>(dcur, a.pooled, a.q, N, D, a.dpooled, a.dq);
-  HIPREC_TRY(hipGetLastError());
-  din_fill_kernel<<<grid_for_threads(a.zero_floats), kBlock, 0, st>>>(a.dU, a.zero_floats, 0.f);
-  HIPREC_TRY(hipGetLastError());
+  const DinTower tw = din_tower_of(q, o, a);
+  if (int rc = din_tower_forward(tw, w_flat, bn, update_running, train, a.z, a.lc, N, logits_out, stats, st)) return rc;
+  if (!train) return 0;
+  float* dcur = nullptr;
+  if (int rc = din_tower_backward(tw, w_flat, g_flat, a.z, a.lc, label, N, logits_out, scratch, stats, st, &dcur)) return rc;
+  if (int rc = din_z_bwd(dcur, a.pooled, a.q, N, D, a.dpooled, a.dq, st)) return rc;
+  if (int rc = din_fill(a.dU, a.zero_floats, 0.f, st)) return rc;
 
   DinUnit u{};
   const size_t lds = din_plan_lds(q, true, &u);
@@ -1089,9 +1137,7 @@ int din_run(const DinDims& q, const float* w_flat, float* g_flat, float* bn, int
   din_unit_bwd_kernel<<<n_slabs, kBlock, lds, st>>>(u, B, a.a, a.dpooled, seq, a.dU, a.dV, a.dq, g_flat, nullptr, a.slabs);
   HIPREC_TRY(hipGetLastError());
   if (int rc = din_unit_finish(q, o, a, BT, N, n_slabs, g_flat + o.a0w, a.drows, a.dqv, st)) return rc;
-  din_scatter_kernel<<<grid_for_waves(BT + N), kBlock, 0, st>>>(a.drows, a.dqv, a.dq, seq, cand, a.lv, a.lc, BT, N, D, g_flat);
-  HIPREC_TRY(hipGetLastError());
-  return 0;
+  return din_scatter(a.drows, a.dqv, a.dq, seq, cand, a.lv, a.lc, BT, N, D, g_flat, st);
 }
 
 }  // namespace
@@ -1166,17 +1212,14 @@ extern "C" int hiprec_din_attention(const hiprec_din_shape* shape, const float* 
   DinWs w = din_carve_ws(static_cast<float*>(workspace), q, batch, n_cand, bwd);
   const int64_t BT = batch * q.T, N = batch * n_cand;
   if (int rc = din_prep(q, o, w_flat, w, st)) return rc;
-  din_flags_kernel<<<grid_for_threads(BT + N), kBlock, 0, st>>>(mask, w.lv, BT, w.lc, N);
-  HIPREC_TRY(hipGetLastError());
+  if (int rc = din_flags(mask, w.lv, BT, w.lc, N, st)) return rc;
   w.rows = const_cast<float*>(e);
   w.q = const_cast<float*>(q_rows);
   if (int rc = din_unit_forward(q, o, w_flat, w, batch, n_cand, pooled, a, st)) return rc;
   if (!bwd) return 0;
   // the stage's backward from d pooled alone: the unit's parameters into g_att, d e [B T, D] and d q [N, D] as rows
-  din_fill_kernel<<<grid_for_threads(w.zero_floats), kBlock, 0, st>>>(w.dU, w.zero_floats, 0.f);
-  HIPREC_TRY(hipGetLastError());
-  din_fill_kernel<<<grid_for_threads(N * q.D), kBlock, 0, st>>>(dq, N * q.D, 0.f);
-  HIPREC_TRY(hipGetLastError());
+  if (int rc = din_fill(w.dU, w.zero_floats, 0.f, st)) return rc;
+  if (int rc = din_fill(dq, N * q.D, 0.f, st)) return rc;
   DinUnit u{};
   const size_t lds = din_plan_lds(q, true, &u);
   u.C = static_cast<int>(n_cand);
@@ -1187,9 +1230,6 @@ extern "C" int hiprec_din_attention(const hiprec_din_shape* shape, const float* 
   HIPREC_TRY(hipGetLastError());
   const int D = q.D;
   if (int rc = din_unit_finish(q, o, w, BT, N, n_slabs, g_att, de, w.dqv, st)) return rc;      // the GEMM's part of d e
-  din_add_kernel<<<grid_for_threads(BT * D), kBlock, 0, st>>>(de, w.drows, BT * D);      // the part summed on chip
-  HIPREC_TRY(hipGetLastError());
-  din_add_kernel<<<grid_for_threads(N * D), kBlock, 0, st>>>(dq, w.dqv, N * D);
-  HIPREC_TRY(hipGetLastError());
-  return 0;
+  if (int rc = din_add(de, w.drows, BT * D, st)) return rc;      // the part summed on chip
+  return din_add(dq, w.dqv, N * D, st);
 }

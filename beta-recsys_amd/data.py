@@ -524,6 +524,21 @@ class CandidateLoader:
                    torch.from_numpy(label[:rows.size].copy()))
 
 
+class EvolutionLoader(CandidateLoader):
+    """DIEN's batches: ``CandidateLoader``'s with ``neg_seq [B, maxlen]`` behind ``seq``, i.e. ``(seq, neg_seq, cand, label)``.
+    ``neg_seq`` holds one item per position, uniform over ``1 .. n_items`` and different from the item at that position, 0
+    where ``seq`` is 0; it is redrawn at every iteration from the loader's seeded generator."""
+
+    def negatives(self, seq):
+        seq = np.asarray(seq, dtype=np.int64)
+        neg = self._rng.integers(1, self.n_items, seq.shape)
+        return np.where(seq != 0, neg + (neg >= seq), 0)
+
+    def __iter__(self):
+        for seq, cand, label in super().__iter__():
+            yield seq, torch.from_numpy(self.negatives(seq.numpy())), cand, label
+
+
 # ---- session-parallel mini-batches for GRU4Rec (Hidasi et al., ICLR 2016, section 3.1) -------------------------------------
 class SessionParallelLoader:
     """``batch_size`` slots each walk one session, one event per step; a step is ``(in_items [B], targets [B],

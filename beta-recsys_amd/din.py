@@ -45,7 +45,52 @@ class _Layer(nn.Module):
             self.alpha = Parameter(alpha, requires_grad=False)
 
 
-class DIN(_FlatModel):
+class _RankingModel(_FlatModel):
+    """What the ranking models share: Dice's running buffers beside the flat buffer, ``seq`` / ``cand`` as device tensors,
+    ``predict``.  A subclass builds ``dnn`` / ``dnn_hidden`` / ``dnn_activation`` and defines ``forward(seqs, cand)``."""
+
+    # ---- Dice's running buffers: a second flat buffer, [running_mean, running_var] per tower layer ----------------------------
+    def _bind_running(self, flat):
+        self._bn = flat
+        at = 0
+        for layer, w in zip(self.dnn, self.dnn_hidden):
+            if self.dnn_activation == "dice":
+                layer.register_buffer("running_mean", flat[at:at + w])
+                layer.register_buffer("running_var", flat[at + w:at + 2 * w])
+            at += 2 * w
+
+    def _apply(self, fn, recurse=True):
+        super()._apply(fn)
+        moved = fn(self._bn)
+        if moved is not self._bn:
+            self._bind_running(moved.contiguous())
+        return self
+
+    def sequences(self, seqs):
+        """``[B, L <= maxlen]`` ids as ``(flat int64 device tensor [B * maxlen], B)``, left-padded with 0."""
+        shape = tuple(seqs.shape) if torch.is_tensor(seqs) else np.asarray(seqs).shape
+        if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
+            raise ValueError("sequences must be [batch >= 1, length >= 1]")
+        B, L, T = int(shape[0]), int(shape[1]), self.maxlen
+        if L > T:
+            raise ValueError(f"sequence length {L} exceeds maxlen {T}")
+        flat = index_tensor(seqs, self._flat.device)
+        if L < T:
+            flat = torch.nn.functional.pad(flat.view(B, L), (T - L, 0)).reshape(-1).contiguous()
+        return flat, B
+
+    def candidates(self, cand, B):
+        """``[B, C >= 1]`` ids as ``(flat int64 device tensor, C)``."""
+        shape = tuple(cand.shape) if torch.is_tensor(cand) else np.asarray(cand).shape
+        if len(shape) != 2 or shape[0] != B or shape[1] < 1:
+            raise ValueError(f"candidates must be [{B}, n >= 1]: a list for every sequence")
+        return index_tensor(cand, self._flat.device), int(shape[1])
+
+    def predict(self, seqs, cand):
+        return self.forward(seqs, cand)
+
+
+class DIN(_RankingModel):
     """Flat buffer in ``state_dict()`` order: ``item_emb.weight``, ``att.{0,1}.{weight,bias,alpha}``, ``att.2.{weight,bias}``,
     ``dnn.l.{weight,bias,alpha}``, ``out.{weight,bias}``; with ``dice`` every ``dnn.l`` also holds the buffers
     ``running_mean`` / ``running_var`` (views of a second flat buffer).  The unit's alphas are read under ``prelu`` only."""
@@ -102,23 +147,6 @@ class DIN(_FlatModel):
         self._bind_running(torch.cat([torch.cat([torch.zeros(w), torch.ones(w)]) for w in dnn]))
         self._ws = None
 
-    # ---- Dice's running buffers: a second flat buffer, [running_mean, running_var] per tower layer ----------------------------
-    def _bind_running(self, flat):
-        self._bn = flat
-        at = 0
-        for layer, w in zip(self.dnn, self.dnn_hidden):
-            if self.dnn_activation == "dice":
-                layer.register_buffer("running_mean", flat[at:at + w])
-                layer.register_buffer("running_var", flat[at + w:at + 2 * w])
-            at += 2 * w
-
-    def _apply(self, fn, recurse=True):
-        super()._apply(fn)
-        moved = fn(self._bn)
-        if moved is not self._bn:
-            self._bind_running(moved.contiguous())
-        return self
-
     # ---- device-side plumbing --------------------------------------------------------------------------------
     def workspace(self, lib, batch, n_cand, train):
         need = lib.hiprec_din_workspace_bytes(ctypes.byref(self.shape), int(batch), int(n_cand), int(train))
@@ -134,26 +162,6 @@ class DIN(_FlatModel):
         _lib.check(_lib.load().hiprec_din_tiles(ctypes.byref(self.shape), out))
         return dict(zip(("tile", "chunk_fwd", "chunk_bwd", "slice", "slabs", "resident_fwd", "resident_bwd"), out))
 
-    def sequences(self, seqs):
-        """``[B, L <= maxlen]`` ids as ``(flat int64 device tensor [B * maxlen], B)``, left-padded with 0."""
-        shape = tuple(seqs.shape) if torch.is_tensor(seqs) else np.asarray(seqs).shape
-        if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
-            raise ValueError("sequences must be [batch >= 1, length >= 1]")
-        B, L, T = int(shape[0]), int(shape[1]), self.maxlen
-        if L > T:
-            raise ValueError(f"sequence length {L} exceeds maxlen {T}")
-        flat = index_tensor(seqs, self._flat.device)
-        if L < T:
-            flat = torch.nn.functional.pad(flat.view(B, L), (T - L, 0)).reshape(-1).contiguous()
-        return flat, B
-
-    def candidates(self, cand, B):
-        """``[B, C >= 1]`` ids as ``(flat int64 device tensor, C)``."""
-        shape = tuple(cand.shape) if torch.is_tensor(cand) else np.asarray(cand).shape
-        if len(shape) != 2 or shape[0] != B or shape[1] < 1:
-            raise ValueError(f"candidates must be [{B}, n >= 1]: a list for every sequence")
-        return index_tensor(cand, self._flat.device), int(shape[1])
-
     def forward(self, seqs, cand):
         """Logits ``[B, C]`` of the candidates (0 in dead slots); Dice reads its running statistics."""
         lib = self._require_hip()
@@ -168,9 +176,6 @@ class DIN(_FlatModel):
                                        _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
         self._check_status()
         return out
-
-    def predict(self, seqs, cand):
-        return self.forward(seqs, cand)
 
     def attention_stage(self, e, q, mask, dpooled=None):
         """The activation unit and the pooling alone on explicit rows: ``e [B, maxlen, D]`` stands where ``item_emb[seq]``
@@ -204,17 +209,72 @@ class DIN(_FlatModel):
         return pooled, a, grads, de, dq
 
 
-class DINEngine(FlatModelEngine):
+class _RankingEngine(FlatModelEngine):
+    """What the ranking engines share: the step around a subclass's ``_enqueue_grad``, the epoch loop, ``predict`` and
+    ``rerank``."""
+
+    def __init__(self, config, model):
+        self.config = config
+        self.model = model
+        self.last_logits = None
+        super().__init__(config)
+        self._n_batches = 0
+        self._update_running = True
+
+    def train_single_batch(self, batch_data, ratings=None):
+        """One step on the model's batch: the loss (the mean over the live candidates).  Moves Dice's running buffers."""
+        assert hasattr(self, "model"), "Please specify the exact model !"
+        self._enqueue_grad(batch_data)
+        self._enqueue_opt()
+        return self._sync_stats().loss
+
+    def backward_only(self, batch_data):
+        """``(loss, grads)`` without the optimizer step; Dice's running buffers stay as they are."""
+        self._update_running = False
+        try:
+            return super().backward_only(batch_data)
+        finally:
+            self._update_running = True
+
+    def _epoch_step(self, batch):
+        self._n_batches += 1
+        self._enqueue_step(batch)
+
+    def train_an_epoch(self, train_loader, epoch_id):
+        """Every batch of the loader enqueued back to back with ONE host sync at the end; returns
+        the mean of the per-step losses and writes it to the writer."""
+        assert hasattr(self, "model"), "Please specify the exact model !"
+        self._n_batches = 0
+        st = self._run_epoch(train_loader)
+        mean_loss = st.loss_sum / max(self._n_batches, 1)
+        print("[Training Epoch {}], Loss {:.6f}".format(epoch_id, mean_loss))
+        self.writer.add_scalar("model/loss", mean_loss, epoch_id)
+        return mean_loss
+
+    # ---- inference ---------------------------------------------------------------------------------------------
+    def predict(self, seqs, cand):
+        """Eval-mode logits ``[B, C]`` of every sequence's own candidate list (0 in dead slots)."""
+        self.model.eval()
+        return self.model.predict(seqs, cand)
+
+    def rerank(self, seqs, cand, k):
+        """The ``k`` best live candidates of every row by ``predict``: ``(items [B, k] int64, logits [B, k])``, best first,
+        ``-1`` / ``-inf`` where a row has fewer than ``k`` live candidates."""
+        logits = self.predict(seqs, cand)
+        ids = index_tensor(cand, logits.device).view(logits.shape)
+        if not 1 <= int(k) <= logits.shape[1]:
+            raise ValueError(f"k must be in 1 .. {logits.shape[1]}")
+        top, at = torch.where(ids != 0, logits, torch.full_like(logits, -float("inf"))).topk(int(k), dim=1)
+        items = torch.gather(ids, 1, at)
+        return torch.where(torch.isinf(top), torch.full_like(items, -1), items), top
+
+
+class DINEngine(_RankingEngine):
     """``train_single_batch((seq, cand, label)) -> float``, ``backward_only``, ``train_an_epoch(loader, epoch_id)``,
     ``predict``, ``rerank``; optimizers and checkpoints through the flat-model base."""
 
     def __init__(self, config):
-        self.config = config
-        self.model = DIN(config["model"])
-        self.last_logits = None
-        super(DINEngine, self).__init__(config)
-        self._n_batches = 0
-        self._update_running = True
+        super().__init__(config, DIN(config["model"]))
 
     def _alloc_extra(self, lib, dev):
         m = self.model
@@ -241,50 +301,3 @@ class DINEngine(FlatModelEngine):
             ctypes.byref(m.shape), _lib.ptr(m.flat), _lib.ptr(self._g_flat), _lib.ptr(m._bn), int(self._update_running),
             _lib.ptr(seq_t), _lib.ptr(cand_t), _lib.ptr(lab_t), B, C, _lib.ptr(self.last_logits), _lib.ptr(self._stats),
             _lib.ptr(self._scratch), self._scratch.numel(), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-
-    def train_single_batch(self, batch_data, ratings=None):
-        """One step on ``(seq, cand, label)``: the loss (the mean over the live candidates).  Moves Dice's running buffers."""
-        assert hasattr(self, "model"), "Please specify the exact model !"
-        self._enqueue_grad(batch_data)
-        self._enqueue_opt()
-        return self._sync_stats().loss
-
-    def backward_only(self, batch_data):
-        """``(loss, grads)`` without the optimizer step; Dice's running buffers stay as they are."""
-        self._update_running = False
-        try:
-            return super().backward_only(batch_data)
-        finally:
-            self._update_running = True
-
-    def _epoch_step(self, batch):
-        self._n_batches += 1
-        self._enqueue_step(batch)
-
-    def train_an_epoch(self, train_loader, epoch_id):
-        """Every batch of the loader (``data.CandidateLoader``) enqueued back to back with ONE host sync at the end; returns
-        the mean of the per-step losses and writes it to the writer."""
-        assert hasattr(self, "model"), "Please specify the exact model !"
-        self._n_batches = 0
-        st = self._run_epoch(train_loader)
-        mean_loss = st.loss_sum / max(self._n_batches, 1)
-        print("[Training Epoch {}], Loss {:.6f}".format(epoch_id, mean_loss))
-        self.writer.add_scalar("model/loss", mean_loss, epoch_id)
-        return mean_loss
-
-    # ---- inference ---------------------------------------------------------------------------------------------
-    def predict(self, seqs, cand):
-        """Eval-mode logits ``[B, C]`` of every sequence's own candidate list (0 in dead slots)."""
-        self.model.eval()
-        return self.model.predict(seqs, cand)
-
-    def rerank(self, seqs, cand, k):
-        """The ``k`` best live candidates of every row by ``predict``: ``(items [B, k] int64, logits [B, k])``, best first,
-        ``-1`` / ``-inf`` where a row has fewer than ``k`` live candidates."""
-        logits = self.predict(seqs, cand)
-        ids = index_tensor(cand, logits.device).view(logits.shape)
-        if not 1 <= int(k) <= logits.shape[1]:
-            raise ValueError(f"k must be in 1 .. {logits.shape[1]}")
-        top, at = torch.where(ids != 0, logits, torch.full_like(logits, -float("inf"))).topk(int(k), dim=1)
-        items = torch.gather(ids, 1, at)
-        return torch.where(torch.isinf(top), torch.full_like(items, -1), items), top

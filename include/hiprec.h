@@ -2215,6 +2215,73 @@ int hiprec_din_attention(const hiprec_din_shape* shape, const float* w_flat, con
                          const uint8_t* mask, int64_t batch, int64_t n_cand, float* pooled, float* a, const float* dpooled,
                          float* g_att, float* de, float* dq, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ================= DIEN (Deep Interest Evolution Network, Zhou et al., AAAI 2019; no counterpart in the reference:
+ * tests/dien_torch.py is the restatement) ====================================================================================
+ * DIN's successor: ids, seq / cand / label and the tower as DIN's; neg_seq [batch, maxlen] int64 holds one sampled item per
+ * position (0 where seq is 0).  D = dim is also the hidden width of both recurrent layers.  The parameters live in ONE
+ * flat buffer in state_dict() order: item_emb.weight [n_items + 1, D] (row 0 is zero and receives no gradient);
+ * extractor.weight_ih, extractor.weight_hh [3D, D], extractor.bias [3D]; att.weight [D, D]; evolve.weight_ih,
+ * evolve.weight_hh [3D, D], evolve.bias [3D] (gate order r | u | n); the tower as DIN's with in_0 = 3 D; `running` as DIN's.
+ * Step of a layer at a live position (seq[b, t] != 0; a dead position leaves h unchanged), h = 0 at the start:
+ *   r = sigmoid(W_r x + U_r h + b_r), u = sigmoid(W_u x + U_u h + b_u), n = tanh(W_n x + r * (U_n h) + b_n),
+ *   h <- (1 - g u) h + g u n.
+ * Extractor: g = 1, x_t = E[seq[b, t]], one state per sequence, h1[b, t] = the state after t.  Attention: s[b, c, t] =
+ * h1[b, t] . (att.weight E[cand[b, c]]), a = softmax of s over the live positions, exactly 0 at dead ones.  Evolution:
+ * g = a[b, c, t], x_t = h1[b, t], one state per (sequence, candidate), hT = the state after T - 1.  z = [hT, q, hT * q]
+ * into the tower; L_target = BCE-with-logits, the mean over the live candidates.  L_aux = the mean over t < T - 1 with
+ * seq[b, t], seq[b, t + 1], neg_seq[b, t + 1] all non-zero of softplus(-h1[b, t] . E[seq[b, t + 1]]) + softplus(h1[b, t] .
+ * E[neg_seq[b, t + 1]]) (0 without a term).  Loss = L_target + aux_weight L_aux.
+ * Limits: D a multiple of 16 in 16 .. 128, T in 1 .. 256, 1 .. 3 tower widths in 1 .. 512, batch * maxlen <= 2^24, batch *
+ * n_cand <= 2^24 and, when training, batch * n_cand * maxlen <= 2^24: the rows of the saved gates are counted in 32 bits
+ * through the weight-gradient GEMMs, so a training batch is bounded by this and not by the workspace alone (at D 16 the bound
+ * is reached at 5.4 GB of saved rows). */
+typedef struct hiprec_dien_shape {
+  int64_t n_items;
+  int32_t dim;
+  int32_t maxlen;
+  int32_t dnn_act; /* 0 dice, 1 prelu */
+  int32_t n_dnn;
+  int32_t dnn[3];
+  float aux_weight;
+} hiprec_dien_shape;
+size_t hiprec_dien_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_dien_param_floats(const hiprec_dien_shape* shape);
+/* out[8]: rows of a recurrence tile; sequences a tile can touch and the slabs of a per-sequence sum at n_cand candidates;
+ * K-slices of d weight_hh; rows of weight_hh [3D, D] resident in LDS (the rest is read through L2) in the extractor's and the
+ * evolution layer's forward, then in their backward */
+int hiprec_dien_tiles(const hiprec_dien_shape* shape, int64_t n_cand, int32_t* out);
+/* bytes of device workspace of a call (0: unsupported).  mode bit 0: with the backward's buffers (the saved gates and states:
+ * 5 D floats per (sequence, position) and per (sequence, candidate, position)); bit 1: of hiprec_dien_evolve; bit 2 (4 / 5):
+ * of hiprec_dien_extract */
+size_t hiprec_dien_workspace_bytes(const hiprec_dien_shape* shape, int64_t batch, int64_t n_cand, int32_t mode);
+/* ---- zero_grad + forward + loss + backward of one training step as a fixed sequence of launches, no host sync; the
+ * contract of hiprec_din_grad with neg_seq beside seq.  item_emb.weight receives row atomics, every other gradient is the
+ * same bits on every run.  An id outside [0, n_items] in seq, neg_seq or cand sets HIPREC_STATUS_ITEM_OOB. */
+int hiprec_dien_grad(const hiprec_dien_shape* shape, const float* w_flat, float* g_flat, float* running,
+                     int32_t update_running, const int64_t* seq, const int64_t* neg_seq, const int64_t* cand,
+                     const float* label, int64_t batch, int64_t n_cand, float* logits_out, hiprec_stats* stats, void* scratch,
+                     size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
+/* the eval forward: logits_out [batch, n_cand], 0 in dead slots; Dice reads the running buffers; nothing is saved */
+int hiprec_dien_score(const hiprec_dien_shape* shape, const float* w_flat, float* running, const int64_t* seq,
+                      const int64_t* cand, int64_t batch, int64_t n_cand, float* logits_out, hiprec_stats* stats,
+                      void* workspace, size_t workspace_bytes, void* stream);
+/* the evolution layer alone (attention + AUGRU) on explicit rows h1 [batch, maxlen, D], q_rows [batch, n_cand, D] and mask
+ * [batch, maxlen] (any pattern): hT [batch, n_cand, D] and a [batch, n_cand, maxlen], exactly 0 where the mask is.  With dhT
+ * [batch, n_cand, D] also its backward: the gradients of att.weight, evolve.weight_ih, evolve.weight_hh, evolve.bias into
+ * g_att (zero on entry, laid out like that span of the flat buffer), dh1 [batch, maxlen, D] and dq [batch, n_cand, D]. */
+int hiprec_dien_evolve(const hiprec_dien_shape* shape, const float* w_flat, const float* h1, const float* q_rows,
+                       const uint8_t* mask, int64_t batch, int64_t n_cand, float* hT, float* a, const float* dhT, float* g_att,
+                       float* dh1, float* dq, void* workspace, size_t workspace_bytes, void* stream);
+/* the interest extractor alone (the recurrence at one candidate, g = 1) on explicit rows x [batch, maxlen, D] and mask [batch,
+ * maxlen] (any pattern): h1 [batch, maxlen, D], the state after every position (the carried state at a dead one).  With dh1
+ * [batch, maxlen, D] (read at the live positions only, as nothing in the model reads a dead one) also its backward: the
+ * gradients of extractor.weight_ih, extractor.weight_hh, extractor.bias into g_ext (zero on entry, laid out like that span of
+ * the flat buffer) and dx [batch, maxlen, D].  No auxiliary loss.  Workspace: mode 4 / 5, n_cand ignored. */
+int hiprec_dien_extract(const hiprec_dien_shape* shape, const float* w_flat, const float* x, const uint8_t* mask,
+                        int64_t batch, float* h1, const float* dh1, float* g_ext, float* dx, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ================= VBCAR (beta_rec/models/vbcar.py) ================================================
  * The parameters live in ONE flat buffer in state_dict() order: user_emb [n_users, emb_dim], item_emb [n_items, emb_dim],
  * fc_u_1_mu.weight [late_dim, fea_u], .bias [late_dim], fc_u_2_mu.weight [2 emb_dim, late_dim], .bias [2 emb_dim], then
