@@ -33,6 +33,7 @@ from .mamba4rec import Mamba4Rec, Mamba4RecEngine, selective_scan  # noqa: F401
 from .comirec import ComiRec, ComiRecEngine  # noqa: F401
 from .din import DIN, DINEngine  # noqa: F401
 from .dien import DIEN, DIENEngine  # noqa: F401
+from .eta import ETA, ETAEngine  # noqa: F401
 from .triple2vec import Triple2vec, Triple2vecEngine  # noqa: F401
 from .vbcar import VBCAR, VBCAREngine  # noqa: F401
 from .vaecf import VAE, VAECFEngine  # noqa: F401

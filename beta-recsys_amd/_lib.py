@@ -301,6 +301,13 @@ class DinShape(Structure):
                 ("att_act", c_int32), ("dnn_act", c_int32), ("n_dnn", c_int32), ("dnn", c_int32 * 3)]
 
 
+class EtaShape(Structure):
+    """hiprec_eta_shape (include/hiprec.h)."""
+
+    _fields_ = [("n_items", c_int64), ("dim", c_int32), ("maxlen", c_int32), ("hash_bits", c_int32), ("top_k", c_int32),
+                ("num_heads", c_int32), ("dnn_act", c_int32), ("n_dnn", c_int32), ("dnn", c_int32 * 3)]
+
+
 class DienShape(Structure):
     """hiprec_dien_shape (include/hiprec.h)."""
 
@@ -766,6 +773,16 @@ SIGNATURES = {
     "hiprec_dien_evolve": (
         c_int, [POINTER(DienShape), _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "hiprec_dien_extract": (c_int, [POINTER(DienShape), _P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "hiprec_eta_shape_bytes": (c_size_t, []),
+    "hiprec_eta_param_floats": (c_int64, [POINTER(EtaShape)]),
+    "hiprec_eta_tiles": (c_int, [POINTER(EtaShape), c_int64, POINTER(c_int32)]),
+    "hiprec_eta_workspace_bytes": (c_size_t, [POINTER(EtaShape), c_int64, c_int64, c_int32]),
+    "hiprec_eta_grad": (
+        c_int, [POINTER(EtaShape), _P, _P, _P, _P, c_int32, _P, _P, _P, c_int64, c_int64, _P, _P, _P, c_size_t, _P, c_size_t,
+                _P]),
+    "hiprec_eta_retrieve": (c_int, [POINTER(EtaShape), _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_size_t, _P]),
+    "hiprec_eta_attention": (
+        c_int, [POINTER(EtaShape), _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "hiprec_vbcar_encode_workspace_bytes": (c_size_t, [POINTER(VbcarShape), c_int64, c_int32]),
     "hiprec_vbcar_grad": (
         c_int,
@@ -1036,6 +1053,8 @@ def load():
         raise RuntimeError("hiprec_din_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_dien_shape_bytes() != ctypes.sizeof(DienShape):
         raise RuntimeError("hiprec_dien_shape layout mismatch between _lib.py and libhiprec.so")
+    if lib.hiprec_eta_shape_bytes() != ctypes.sizeof(EtaShape):
+        raise RuntimeError("hiprec_eta_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_vbcar_shape_bytes() != ctypes.sizeof(VbcarShape):
         raise RuntimeError("hiprec_vbcar_shape layout mismatch between _lib.py and libhiprec.so")
     if lib.hiprec_tvbr_shape_bytes() != ctypes.sizeof(TvbrShape):

@@ -2282,6 +2282,67 @@ int hiprec_dien_extract(const hiprec_dien_shape* shape, const float* w_flat, con
                         int64_t batch, float* h1, const float* dh1, float* g_ext, float* dx, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ================= ETA (End-to-end Target Attention, Chen et al., 2021; no counterpart in the reference:
+ * tests/eta_torch.py is the restatement) ======================================================================================
+ * The ranking model for long histories: ids, seq / cand / label, the tower and `running` as DIN's, maxlen up to 4096.
+ * D = dim, m = hash_bits, k = top_k, H = num_heads, dh = D / H.  hash_weight [m, D] is a constant buffer beside the flat one
+ * (never trained).  The parameters live in ONE flat buffer in state_dict() order: item_emb.weight [n_items + 1, D] (row 0 is
+ * zero and receives no gradient); att.q.weight [D, D], att.q.bias [D], then att.k, att.v, att.o likewise; the tower as DIN's
+ * with in_0 = 3 D.
+ * Fingerprints: bit j of code(x) is 1 iff sum_d hash_weight[j, d] x[d] >= 0 (fp32); a code is m / 32 words, bit j in word
+ * j / 32 at position j % 32.  Retrieval: for every pair and every live position t, ham = popcount(code(q) ^ code(e_t)); the
+ * selection is the k live positions with the smallest (ham, -t); sel [batch, n_cand, k] holds it ascending in t, -1 in the
+ * slots a pair with fewer live positions leaves and in a dead candidate's whole row.  Attention: Qp = q Wq^T + bq, Kp, Vp
+ * likewise from e; per head s_j = <Qp_h, Kp_h[sel_j]> / sqrt(dh) over the live slots, p = softmax(s), o_h = sum_j p_j
+ * Vp_h[sel_j] (0 without a live slot); v = o Wo^T + bo; z = [v, q, v * q] into the tower; BCE-with-logits, the mean over the
+ * live candidates.  The hash has no derivative.
+ * Limits: D a multiple of 16 in 16 .. 128, maxlen in 1 .. 4096, hash_bits in {32, 64, 96, 128}, top_k in 1 .. 128, num_heads
+ * dividing D with dh >= 4, 1 .. 3 tower widths in 1 .. 512, batch * maxlen <= 2^24 and batch * n_cand * top_k <= 2^24. */
+typedef struct hiprec_eta_shape {
+  int64_t n_items;
+  int32_t dim;
+  int32_t maxlen;
+  int32_t hash_bits;
+  int32_t top_k;
+  int32_t num_heads;
+  int32_t dnn_act; /* 0 dice, 1 prelu */
+  int32_t n_dnn;
+  int32_t dnn[3];
+} hiprec_eta_shape;
+size_t hiprec_eta_shape_bytes(void);
+/* floats of the flat parameter buffer (-1 for an unsupported shape; hiprec_last_error names the limit) */
+int64_t hiprec_eta_param_floats(const hiprec_eta_shape* shape);
+/* out[6]: positions of a staged chunk; words of a code; 1 when a sequence's codes stay in LDS during the scan (else they are
+ * read back from the workspace); the bound min(maxlen, n_cand * top_k) on a sequence's compact rows; candidates scanned at a
+ * time by a workgroup (a wave each); K-slices of d [att.k.weight; att.v.weight] */
+int hiprec_eta_tiles(const hiprec_eta_shape* shape, int64_t n_cand, int32_t* out);
+/* bytes of device workspace of a call, stage entries included (0: unsupported); train: with the backward's buffers.  Nothing
+ * in it grows with maxlen but the codes (hash_bits / 8 bytes a position). */
+size_t hiprec_eta_workspace_bytes(const hiprec_eta_shape* shape, int64_t batch, int64_t n_cand, int32_t train);
+/* ---- zero_grad + forward + loss + backward of one training step as a fixed sequence of launches, no host sync; the contract
+ * of hiprec_din_grad with hash_weight beside w_flat (g_flat NULL: the eval forward into logits_out).  item_emb.weight receives
+ * row atomics, every other gradient is the same bits on every run.  An id outside [0, n_items] in seq or cand sets
+ * HIPREC_STATUS_ITEM_OOB and counts as padding / as a dead slot; nothing outside the buffers is read or written. */
+int hiprec_eta_grad(const hiprec_eta_shape* shape, const float* w_flat, const float* hash_weight, float* g_flat, float* running,
+                    int32_t update_running, const int64_t* seq, const int64_t* cand, const float* label, int64_t batch,
+                    int64_t n_cand, float* logits_out, hiprec_stats* stats, void* scratch, size_t scratch_bytes, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* the retrieval alone on explicit rows e [batch, maxlen, D], q_rows [batch, n_cand, D] and mask [batch, maxlen] (any pattern;
+ * every candidate is live): codes_e [batch, maxlen, m / 32] (of every position, live or not), codes_q [batch, n_cand, m / 32]
+ * and sel [batch, n_cand, top_k].  Integers only: the result is a function of the signs of the projections. */
+int hiprec_eta_retrieve(const hiprec_eta_shape* shape, const float* hash_weight, const float* e, const float* q_rows,
+                        const uint8_t* mask, int64_t batch, int64_t n_cand, uint32_t* codes_e, uint32_t* codes_q, int32_t* sel,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* the target attention alone on explicit rows and an explicit sel [batch, n_cand, top_k]: every row strictly ascending in t
+ * with its -1 slots last.  Nothing outside the buffers is read or written for any sel (a value outside [0, maxlen) counts as
+ * -1), but for a row with a repeated position or a -1 before a valid slot the result is undefined: the forward uses those
+ * slots while the row-owner backward, a binary search, loses their part of de.  v [batch, n_cand, D].  With dv [batch, n_cand, D] also its
+ * backward: the gradients of att.{q,k,v,o}.{weight,bias} into g_att (zero on entry, laid out like that span of the flat
+ * buffer), de [batch, maxlen, D] (zero at positions nobody selected) and dq [batch, n_cand, D]. */
+int hiprec_eta_attention(const hiprec_eta_shape* shape, const float* w_flat, const float* e, const float* q_rows,
+                         const int32_t* sel, int64_t batch, int64_t n_cand, float* v, const float* dv, float* g_att, float* de,
+                         float* dq, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ================= VBCAR (beta_rec/models/vbcar.py) ================================================
  * The parameters live in ONE flat buffer in state_dict() order: user_emb [n_users, emb_dim], item_emb [n_items, emb_dim],
  * fc_u_1_mu.weight [late_dim, fea_u], .bias [late_dim], fc_u_2_mu.weight [2 emb_dim, late_dim], .bias [2 emb_dim], then
